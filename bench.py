@@ -14,7 +14,7 @@ Two launch shapes run the same steps (bit for bit, tests/test_gpu_api.py):
       the env state in registers between the steps of a launch, every step's outputs in
       its ring slot -- the step-only workload of config 3 (no host policy in the loop);
   --launch step: one lb_step launch per vector step (k_step_tpe), the VecEnv.step() shape
-      a host/NN policy needs; measured in the same run and reported under "lb_step".
+      a host/NN policy needs; with --full measured in the same run and reported under "lb_step".
 
 Episodes are staggered before timing (env i starts at step i mod episode_length), so every
 timed step ends and auto-resets 1/episode_length of the envs — the steady state of a
@@ -26,7 +26,13 @@ episode_length 100; Philox seed 0), sharded over the GPUs: rank r owns global en
 [r*B/G, (r+1)*B/G) with no data-path collective ("scaling": "strong").  --weak keeps
 --envs per GPU instead.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps and prints the result line.  --full adds
+  what takes runs of its own: the lb_step measurement of the same window ("lb_step") and the
+  CPU baselines ("cpu_baseline": the C oracle under OpenMP, the SubprocVecEnv pattern).
+  --dump-outputs DIR: what the last timed step returned (observations, rewards, dones, the
+  terminal observations and episode-statistics rows), as DIR/<name>.npy; the inputs are
+  the same from run to run (Philox seed 0), so two builds compare output for output.
   With --gpus N > 1 and no torchrun environment, bench.py launches N ranks itself
   (torch.distributed.run, 127.0.0.1) before touching the GPU and exits with their status.
   --plan-only: the launcher / sharding / statistics-reduction path without a GPU (gloo).
@@ -81,11 +87,15 @@ def parse(argv):
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly")
     ap.add_argument("--launch", default="rollout", choices=("rollout", "step"),
                     help="rollout: K = ring steps per lb_rollout launch; step: one lb_step per step")
-    ap.add_argument("--no-step-line", action="store_true", help="rollout mode: skip the lb_step measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the lb_step launch shape and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-step-line", action="store_true", help="--full, rollout mode: skip the lb_step measurement")
     ap.add_argument("--lockstep", action="store_true", help="do not stagger episodes (all envs reset together)")
     ap.add_argument("--geometry", default="auto", choices=("auto", "tpe", "slice"), help="E <= 8 kernel shape")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--plan-only", action="store_true", help="launcher + sharding + stats reduction, no GPU")
     ap.add_argument("--pmc-json", default=os.path.join(REPO, "profiles", "pmc_traffic.json"))
     return ap.parse_args(argv)
@@ -126,6 +136,47 @@ def cpu_baseline(cfg_kwargs, seconds):
                                "sample": "the reference env under an 8-worker pipe VecEnv, survey container "
                                          "(BASELINE.md; the reference does not travel to the GPU box)"}
     return out
+
+
+DUMP_OBS_BYTES = 16 << 20  # per observation array; the whole dump stays under 64 MB
+DUMP_ROWS = 1 << 20  # rewards / dones: every env up to this many
+
+
+def _dump_ids(B, n):
+    """n of the B env rows: all of them, or a fixed (seed 0) sorted sample."""
+    import numpy as np
+    if n >= B:
+        return np.arange(B, dtype=np.int64)
+    return np.sort(np.random.RandomState(0).choice(B, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, env, obs_ring, rew_ring, done_ring, slot, rank, world):
+    """What the caller of the timed path holds after its last step (ring slot `slot`): the
+    observations, rewards and dones of that step, and the env's terminal-observation and
+    episode-statistics buffers (rows of the envs that finished are that step's).  Wide arrays
+    are cut to a fixed sample of env rows (their local ids in obs_env_ids / env_ids)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    B, R = obs_ring.shape[1], obs_ring.shape[2]
+    wide = _dump_ids(B, max(1, DUMP_OBS_BYTES // (R * 32)))
+    rows = _dump_ids(B, DUMP_ROWS)
+    wide_t = torch.from_numpy(wide).to(obs_ring.device)
+    rows_t = torch.from_numpy(rows).to(obs_ring.device)
+    arrays = {
+        "obs": obs_ring[slot][wide_t].cpu().numpy().astype(np.float32),
+        "terminal_obs": env.terminal_obs[wide_t].cpu().numpy().astype(np.float32),
+        "ep_stats": env.ep_stats[wide_t].cpu().numpy().astype(np.float64),
+        "obs_env_ids": wide.astype(np.float64),
+        "reward": rew_ring[slot][rows_t].cpu().numpy().astype(np.float32),
+        "done": done_ring[slot][rows_t].cpu().numpy().astype(np.float32),
+        "env_ids": rows.astype(np.float64),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
 
 
 def plan_only(args, rank, world):
@@ -321,7 +372,9 @@ def main(argv=None):
 
     K = args.steps
     res = measure(args.launch)
-    step_res = measure("step") if args.launch == "rollout" and not args.no_step_line else None
+    if args.dump_outputs:  # (before the lb_step measurement reuses the ring)
+        dump_outputs(args.dump_outputs, env, obs_ring, rew_ring, done_ring, (args.warmup + K - 1) % T, rank, world)
+    step_res = measure("step") if args.full and args.launch == "rollout" and not args.no_step_line else None
     el, kernel_ms, resets = res["el"], res["kernel_ms"], res["resets"]
     launches = res["launches"]
     assert sum(launches) == K, (launches, K)
@@ -402,7 +455,7 @@ def main(argv=None):
                            "frac": b_step * B / (ks * 1e-3) / 1e9 / HBM_PEAK_GBS,
                            "kernel": "k_step_tpe (lb_step, auto-reset inside)" if tpe else "k_step_slice (lb_step)",
                            "resets_in_window": step_res["resets"]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(cfg_kwargs, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -107,14 +107,15 @@ PY
     tail -n 3 gpurun_out/${TAG}_smoke.log
     : > gpurun_out/${TAG}_bench_k20.jsonl
     for r in 1 2 3; do
-      $T 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 >> gpurun_out/${TAG}_bench_k20.jsonl 2>>gpurun_out/${TAG}_bench.err || exit 1
+      bash "$0" bench ${TAG}_bench_k20.jsonl --full --gpus 1 --steps 20 --warmup 5 > /dev/null || exit 1
     done
-    $T 400 python3 bench.py --steps 300 --warmup 100 --no-cpu-baseline > gpurun_out/${TAG}_bench_k100.json 2>>gpurun_out/${TAG}_bench.err || exit 1
+    # (the bench step appends: TAG is a fresh one, so these files hold one line each)
+    bash "$0" bench ${TAG}_bench_k100.json --full --steps 300 --warmup 100 --no-cpu-baseline > /dev/null || exit 1
     $T 400 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_prof_bench -o run --output-format csv -- \
       python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_bench_k20_under_rocprof.json \
       2>gpurun_out/${TAG}_prof_bench.err || exit 1
     bash "$0" pmc $TAG 20 && bash "$0" pmc $TAG 100 && bash "$0" sizes $TAG || exit 1
-    $T 400 python3 bench.py --config e64_multi --steps 300 --warmup 100 --no-cpu-baseline > gpurun_out/${TAG}_bench_e64.json 2>>gpurun_out/${TAG}_bench.err || exit 1
+    bash "$0" bench ${TAG}_bench_e64.json --full --config e64_multi --steps 300 --warmup 100 --no-cpu-baseline > /dev/null || exit 1
     python3 - $TAG <<'PY'
 import json, sys
 tag = sys.argv[1]
