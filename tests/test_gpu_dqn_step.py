@@ -4,6 +4,10 @@ dones, terminal observations and episode-statistics rows, the replay rows, obs <
 the finished-episode sums, the device step / slot words, and the env state afterwards --
 over enough steps that both the explore and the greedy branch run and episodes end.
 Reference: envs/dqn_deepset.py:122-174 (the vector step the three launches restate).
+
+Both sides here are HIP kernels of this project.  The direct comparison of the one-launch step
+with the C oracle and a float64 Q network (odd B, R from 2 to 16, masks, n up to 32, all-explore
+and all-greedy launches) is tests/test_gpu_dqn_oracle.py.
 """
 import pytest
 import torch

@@ -5,6 +5,10 @@ lb_rollout_kernel), then checks one launch of K vector steps against K single st
 already-verified step kernel (lb_policy + lb_step, themselves == the C oracle in
 test_gpu_parity.py), bit for bit: obs, reward, done, actions, terminal obs, episode-stats
 rows, the accumulators and the env fields afterwards, and the env going on from there.
+
+Both sides here are HIP kernels of this project.  The direct comparison of the lean kernels with
+the C oracle (episode_length == K and != K, the driver's K = 20 of L = 100, K = 32 / 33 on the
+two sides of LEAN_SPLIT_MAX_K) is tests/test_gpu_lean_oracle.py.
 """
 import pytest
 import torch
