@@ -889,31 +889,43 @@ unsigned ds_grid(int64_t groups) {
 // gets a block as soon as there are as many groups as CUs
 unsigned ds_grid_spread(int64_t groups) { return (unsigned)std::min<int64_t>(groups, device_cus()); }
 
-template <int MODE>
-void ds_forward_launch(const DSParams& p, hipStream_t s) {
-    if (p.R > LB_DS_MAX_ELEMENTS) {  // large sets: streamed in chunks, one env per wave
-        hipLaunchKernelGGL((k_deepsets_fwd_big<MODE>), dim3(ds_grid(p.B)), dim3(DS_BLOCK), 0, s, p);
-        return;
-    }
+// Which k_deepsets_fwd<TS, P, MODE, XR> (or k_ds_fwd_pair<1, P>) a forward takes: the one rule,
+// shared by ds_forward_launch, lb_ds_forward_pair and lb_ds_forward_kernel (which reports it).
+// ts == 0 is the chunked kernel (k_deepsets_fwd_big).
+struct DSVariant {
+    int ts, P, xr;
+};
+DSVariant ds_forward_variant(int which, int64_t B, int R) {
+    if (R > LB_DS_MAX_ELEMENTS) return {0, 1, 0};  // large sets: streamed in chunks, one env per wave
     // a wave takes P envs per iteration: P = 4 for R <= 16, 2 for R <= 32, else 1 -- fewer
     // when the batch would leave SIMDs of the chip idle (the DQN vector step's 4096 envs:
     // 1,024 groups of four, one per SIMD; its 128-set train step)
-    const int ts = (p.R + 15) / 16;
+    const int ts = (R + 15) / 16;
     // (the greedy-action forward of small sets takes at most two envs per iteration: its Gamma
     // terms on the VALU, the arithmetic of k_dqn_step's Q forward)
-    int P = ts == 1 ? (MODE == 2 ? 2 : 4) : (ts == 2 ? 2 : 1);
-    {
-        const int64_t simds = (int64_t)device_cus() * 4 * LB_DS_WAVES_PER_SIMD;
-        while (P > 1 && (p.B + P - 1) / P < simds) P /= 2;
+    int P = ts == 1 ? (which == LB_DS_FWD_ARGMAX ? 2 : 4) : (ts == 2 ? 2 : 1);
+    const int64_t simds = (int64_t)device_cus() * 4 * LB_DS_WAVES_PER_SIMD;
+    while (P > 1 && (B + P - 1) / P < simds) P /= 2;
+    // the training forward at R = 16 TS + 1 (config 4's 65): TS tiles and the extra row (XR)
+    if (which == LB_DS_FWD_TRAIN && (R == 49 || R == 65)) return {ts - 1, 1, 1};
+    return {ts, P, 0};
+}
+
+template <int MODE>
+void ds_forward_launch(const DSParams& p, hipStream_t s) {
+    static_assert(MODE == LB_DS_FWD || MODE == LB_DS_FWD_TRAIN || MODE == LB_DS_FWD_ARGMAX,
+                  "k_deepsets_fwd's MODE is lb_ds_forward_kernel's `which`");
+    const DSVariant v = ds_forward_variant(MODE, p.B, p.R);
+    if (v.ts == 0) {
+        hipLaunchKernelGGL((k_deepsets_fwd_big<MODE>), dim3(ds_grid(p.B)), dim3(DS_BLOCK), 0, s, p);
+        return;
     }
+    const int ts = v.ts, P = v.P;
     const unsigned grid = ds_grid_spread((p.B + P - 1) / P);
-    if constexpr (MODE == 1) {  // R = 16 TS + 1 (config 4's 65): TS tiles and the extra row (XR)
-        if (p.R == 49) {
-            hipLaunchKernelGGL((k_deepsets_fwd<3, 1, 1, true>), dim3(grid), dim3(DS_BLOCK), 0, s, p);
-            return;
-        }
-        if (p.R == 65) {
-            hipLaunchKernelGGL((k_deepsets_fwd<4, 1, 1, true>), dim3(grid), dim3(DS_BLOCK), 0, s, p);
+    if constexpr (MODE == 1) {
+        if (v.xr) {
+            if (ts == 3) hipLaunchKernelGGL((k_deepsets_fwd<3, 1, 1, true>), dim3(grid), dim3(DS_BLOCK), 0, s, p);
+            else hipLaunchKernelGGL((k_deepsets_fwd<4, 1, 1, true>), dim3(grid), dim3(DS_BLOCK), 0, s, p);
             return;
         }
     }
@@ -1152,6 +1164,23 @@ int lb_ds_train_forward(const float* frag, const float* obs, int64_t num_envs, i
     return check_launch();
 }
 
+int lb_ds_forward_kernel(int32_t which, int64_t num_envs, int32_t num_elements, int32_t* tiles_out,
+                         int32_t* sets_per_wave_out, int32_t* extra_row_out) {
+    if (which < LB_DS_FWD || which > LB_DS_FWD_PAIR) return fail("lb_ds_forward_kernel: unknown forward kind");
+    if (num_envs < 1 || !tiles_out || !sets_per_wave_out || !extra_row_out)
+        return fail("lb_ds_forward_kernel: num_envs < 1 or an output NULL");
+    // (each forward's own bound: a call it would reject has no kernel to name)
+    const int32_t max_r = which == LB_DS_FWD_PAIR ? 16 : which == LB_DS_FWD_TRAIN ? LB_DS_MAX_ELEMENTS_TRAIN
+                                                                                    : LB_DS_MAX_ELEMENTS_FWD;
+    if (num_elements < 1 || num_elements > max_r)
+        return fail("lb_ds_forward_kernel: num_elements out of the forward's range");
+    const DSVariant v = ds_forward_variant(which, num_envs, num_elements);
+    *tiles_out = v.ts;
+    *sets_per_wave_out = v.P;
+    *extra_row_out = v.xr;
+    return 0;
+}
+
 int lb_ds_forward_pair(const float* frag_a, const float* obs_a, float* logits_a, const float* frag_b,
                        const float* obs_b, float* logits_b, float* save_actor_b, float* setvec_b, int64_t num_envs,
                        int32_t num_elements, void* stream) {
@@ -1163,11 +1192,7 @@ int lb_ds_forward_pair(const float* frag_a, const float* obs_a, float* logits_a,
     DSParams b{obs_b, frag_b, logits_b, nullptr, num_envs, num_elements, 1, 0,
                save_actor_b, nullptr, nullptr, setvec_b, nullptr, nullptr};
     // P as ds_forward_launch picks it for one of the two (the batch against the chip's SIMDs)
-    int P = 4;
-    {
-        const int64_t simds = (int64_t)device_cus() * 4 * LB_DS_WAVES_PER_SIMD;
-        while (P > 1 && (num_envs + P - 1) / P < simds) P /= 2;
-    }
+    const int P = ds_forward_variant(LB_DS_FWD_PAIR, num_envs, num_elements).P;
     const int ga = (int)ds_grid_spread((num_envs + P - 1) / P);
     const dim3 grid(2 * ga);
     if (P == 4) hipLaunchKernelGGL((k_ds_fwd_pair<1, 4>), grid, dim3(DS_BLOCK), 0, (hipStream_t)stream, a, b, ga);

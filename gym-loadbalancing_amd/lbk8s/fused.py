@@ -107,6 +107,22 @@ def _launch(frag, x, logits, value):
                                   torch.cuda.current_stream(x.device).cuda_stream))
 
 
+FWD, FWD_TRAIN, FWD_ARGMAX, FWD_PAIR = (_native.LB_DS_FWD, _native.LB_DS_FWD_TRAIN, _native.LB_DS_FWD_ARGMAX,
+                                        _native.LB_DS_FWD_PAIR)
+
+
+def forward_kernel(which, B, R):
+    """(tiles, sets_per_wave, extra_row): the k_deepsets_fwd<TS, P, MODE, XR> (k_ds_fwd_pair<1, P>
+    for FWD_PAIR) that a forward of B sets of R rows takes on the current device; tiles 0 is the
+    chunked kernel (R > 80).  which: FWD (deepsets_forward, q_forward), FWD_TRAIN (fused_train),
+    FWD_ARGMAX (q_argmax_graphable, lb_dqn_act) or FWD_PAIR (fused_train.q_train_with_target).
+    Host only (lb_ds_forward_kernel): the launchers take their choice from the same rule."""
+    ts, p, xr = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    _native.check(_native.lib().lb_ds_forward_kernel(int(which), int(B), int(R), C.byref(ts), C.byref(p),
+                                                     C.byref(xr)))
+    return ts.value, p.value, xr.value
+
+
 @torch.no_grad()
 def deepsets_forward(agent, x: torch.Tensor, require: bool = False):
     """(logits (B, R), value (B,)) of a DeepSetAgent, in one launch when possible."""

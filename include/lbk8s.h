@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LBK8S_ABI_VERSION 14
+#define LBK8S_ABI_VERSION 15
 
 /* reward_function names of loadbalancer_k8s_env.py:20-31 */
 enum { LB_REWARD_NAIVE = 0, LB_REWARD_LATENCY = 1, LB_REWARD_FAIRNESS = 2, LB_REWARD_MULTI = 3 };
@@ -429,6 +429,17 @@ int lb_ds_train_forward(const float* frag, const float* obs, int64_t num_envs, i
 int lb_ds_forward_pair(const float* frag_a, const float* obs_a, float* logits_a, const float* frag_b,
                        const float* obs_b, float* logits_b, float* save_actor_b, float* setvec_b, int64_t num_envs,
                        int32_t num_elements, void* stream);
+
+/* (ABI 15) Which forward kernel a call takes on the current device; host only, no launch:
+ * lb_ds_forward (LB_DS_FWD), lb_ds_train_forward (LB_DS_FWD_TRAIN), lb_ds_q_argmax / lb_dqn_act
+ * (LB_DS_FWD_ARGMAX) or lb_ds_forward_pair (LB_DS_FWD_PAIR) of num_envs sets of num_elements
+ * rows.  The launchers take their choice from the same rule (it weighs num_envs against the
+ * device's CU count).  Refuses a set size the named forward refuses. */
+enum { LB_DS_FWD = 0, LB_DS_FWD_TRAIN = 1, LB_DS_FWD_ARGMAX = 2, LB_DS_FWD_PAIR = 3 };
+int lb_ds_forward_kernel(int32_t which, int64_t num_envs, int32_t num_elements,
+                         int32_t* tiles_out,          /* TS 1..5; 0 = the chunked kernel (R > 80) */
+                         int32_t* sets_per_wave_out,  /* P */
+                         int32_t* extra_row_out);     /* XR (training forward at R = 49 / 65) */
 
 /* PPO loss head (envs/ppo_deepset.py:227-263) for M sets of R <= 257 elements: per-set
  * terms [M,6] (policy term max(pg1, pg2), value term, entropy, approx-kl term, clipped

@@ -3,7 +3,8 @@
 * against the reference modules' own outputs (nn_forward_{e6,e8,e64}.npz, produced by
   envs/deep_sets_agent_original.py / deep_sets_agent_dqn.py on real observations);
 * against the torch modules on the same device for every set size 1..80 (all five
-  set-tile variants, ragged last tiles) with asymmetric random inputs;
+  set-tile variants, ragged last tiles, one set per wave: the variants with 2 and 4 sets per
+  wave are pinned to float64 in test_gpu_ds_variants.py) with asymmetric random inputs;
 * the weight image follows optimizer steps (cache invalidation by parameter version).
 Tolerance: f32 MFMA products are exact, only the summation order differs from the
 torch GEMMs: rtol 1e-4, and an absolute floor of 2e-5 + 4e-6 x max|expected| (a rounding
@@ -44,6 +45,9 @@ def test_fused_forward_matches_reference(name):
 
 @pytest.mark.parametrize("R", [1, 2, 7, 9, 15, 16, 17, 31, 32, 33, 48, 49, 64, 65, 79, 80, 81, 128, 129, 181, 257])
 def test_fused_forward_all_set_sizes(R):
+    """Every set-tile variant (TS 1..5, ragged last tiles) and the chunked kernel -- at one set
+    per wave only: 300 sets leave the chip's SIMDs idle, so the launch demotes P to 1.  The
+    variants with 2 and 4 sets per wave are in test_gpu_ds_variants.py."""
     from lbk8s import fused
     from lbk8s.deepsets import DeepSetAgent
     torch.manual_seed(100 + R)

@@ -20,34 +20,10 @@ import numpy as np
 import pytest
 import torch
 
+from ds_ref import _agent, _inputs  # (the recipes, shared with the variant tests)
 from nn_helpers import close
 
 pytestmark = pytest.mark.gpu
-
-
-def _inputs(B, R, seed, ties=False):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(B, R, 8, generator=g) * torch.linspace(0.5, 3.0, 8) + 0.2
-    x = torch.round(x * 4) / 4
-    if ties:
-        # observation-like structure: request columns equal on every row, integer zone ids,
-        # duplicated rows (exact ties in every set-wise max)
-        x[:, :, 5:] = x[:, :1, 5:]
-        x[:, :, 0] = torch.randint(0, 4, (B, R), generator=g).float()
-        if R > 2:
-            x[:, 1] = x[:, 0]
-    return x
-
-
-def _agent(seed):
-    from lbk8s.deepsets import DeepSetAgent
-    torch.manual_seed(seed)
-    agent = DeepSetAgent(8)
-    with torch.no_grad():  # larger, asymmetric weights than the default init
-        for p in agent.parameters():
-            p.mul_(1.5).add_(0.01)
-            p.copy_(torch.round(p * 32) / 32)
-    return agent
 
 
 def _check(got, exp, what, rtol, rel_floor):

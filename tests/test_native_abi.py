@@ -166,6 +166,55 @@ def test_rollout_kernel_choice():
     assert "Philox" in _native.lib().lb_last_error().decode()
 
 
+def test_ds_forward_kernel_choice():
+    """lb_ds_forward_kernel (host only): the k_deepsets_fwd<TS, P, MODE, XR> / k_ds_fwd_pair<1, P>
+    a forward takes.  P starts at 4 for R <= 16 (2 for the greedy-action forward), 2 for R <= 32,
+    else 1, and halves while ceil(B / P) < 4 x CUs: with C CUs P = 2 needs B >= 8C - 1 and P = 4
+    needs B >= 16C - 3."""
+    import torch
+
+    from lbk8s import _native, fused
+    # (the library's device_cus(): the current device's CU count, 256 without a device)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256
+    F, T, A, P = fused.FWD, fused.FWD_TRAIN, fused.FWD_ARGMAX, fused.FWD_PAIR
+    assert (F, T, A, P) == (0, 1, 2, 3)
+    assert fused.forward_kernel(F, 16 * cus + 3, 9) == (1, 4, 0)
+    assert fused.forward_kernel(F, 16 * cus - 4, 9) == (1, 2, 0)
+    assert fused.forward_kernel(F, 16 * cus - 3, 9) == (1, 4, 0)   # the first batch of 4 C groups of four
+    assert fused.forward_kernel(F, 8 * cus - 2, 9) == (1, 1, 0)
+    assert fused.forward_kernel(F, 8 * cus - 1, 9) == (1, 2, 0)
+    assert fused.forward_kernel(A, 16 * cus + 3, 9) == (1, 2, 0)   # the greedy action: two sets at most
+    assert fused.forward_kernel(T, 16 * cus + 3, 16) == (1, 4, 0)
+    assert fused.forward_kernel(F, 8 * cus + 1, 20) == (2, 2, 0)
+    assert fused.forward_kernel(F, 16 * cus + 3, 32) == (2, 2, 0)
+    assert fused.forward_kernel(A, 8 * cus + 1, 17) == (2, 2, 0)
+    assert fused.forward_kernel(F, 1 << 20, 33) == (3, 1, 0)       # above two tiles: one set per wave
+    assert fused.forward_kernel(T, 300, 65) == (4, 1, 1)           # the extra-row training forward
+    assert fused.forward_kernel(T, 300, 49) == (3, 1, 1)
+    assert fused.forward_kernel(F, 300, 65) == (5, 1, 0)
+    assert fused.forward_kernel(A, 300, 65) == (5, 1, 0)
+    assert fused.forward_kernel(F, 300, 80) == (5, 1, 0)
+    assert fused.forward_kernel(F, 300, 81)[0] == 0                # the chunked kernel
+    assert fused.forward_kernel(T, 300, 257)[0] == 0
+    assert fused.forward_kernel(P, 8 * cus + 1, 9) == (1, 2, 0)
+    assert fused.forward_kernel(P, 16 * cus + 3, 16) == (1, 4, 0)
+    assert fused.forward_kernel(P, 128, 1) == (1, 1, 0)
+    # bad arguments are refused (each forward's own bounds)
+    L = _native.lib()
+    o = [C.c_int32(-1) for _ in range(3)]
+    refs = [C.byref(v) for v in o]
+    for which, B, R in ((-1, 300, 9), (4, 300, 9), (F, 0, 9), (F, 300, 0), (F, 300, 258), (T, 300, 258),
+                        (A, 300, 258), (P, 300, 17)):
+        assert L.lb_ds_forward_kernel(which, B, R, *refs) != 0, (which, B, R)
+        assert b"lb_ds_forward_kernel" in L.lb_last_error()
+        with pytest.raises(RuntimeError):
+            fused.forward_kernel(which, B, R)
+    assert [v.value for v in o] == [-1, -1, -1]                    # (a refused call writes nothing)
+    assert L.lb_ds_forward_kernel(F, 300, 9, None, refs[1], refs[2]) != 0
+    assert L.lb_ds_forward_kernel(F, 300, 9, refs[0], None, refs[2]) != 0
+    assert L.lb_ds_forward_kernel(F, 300, 9, refs[0], refs[1], None) != 0
+
+
 def test_rollout_32bit_offsets_guard():
     """k_rollout_lean / k_rollout_img address with 32-bit byte offsets from scalar bases: a
     launch whose state blob, ep_stats rows or obs slot would pass 4 GiB takes the 64-bit
