@@ -903,6 +903,7 @@ DSVariant ds_forward_variant(int which, int64_t B, int R) {
     const int ts = (R + 15) / 16;
     // (the greedy-action forward of small sets takes at most two envs per iteration: its Gamma
     // terms on the VALU, the arithmetic of k_dqn_step's Q forward)
+    // (the sampling forward is LB_DS_FWD's code up to the logits and the value: its variant too)
     int P = ts == 1 ? (which == LB_DS_FWD_ARGMAX ? 2 : 4) : (ts == 2 ? 2 : 1);
     const int64_t simds = (int64_t)device_cus() * 4 * LB_DS_WAVES_PER_SIMD;
     while (P > 1 && (B + P - 1) / P < simds) P /= 2;
@@ -913,7 +914,8 @@ DSVariant ds_forward_variant(int which, int64_t B, int R) {
 
 template <int MODE>
 void ds_forward_launch(const DSParams& p, hipStream_t s) {
-    static_assert(MODE == LB_DS_FWD || MODE == LB_DS_FWD_TRAIN || MODE == LB_DS_FWD_ARGMAX,
+    static_assert(MODE == LB_DS_FWD || MODE == LB_DS_FWD_TRAIN || MODE == LB_DS_FWD_ARGMAX ||
+                      MODE == LB_DS_FWD_SAMPLE,
                   "k_deepsets_fwd's MODE is lb_ds_forward_kernel's `which`");
     const DSVariant v = ds_forward_variant(MODE, p.B, p.R);
     if (v.ts == 0) {
@@ -969,6 +971,22 @@ int lb_ds_q_argmax(const float* frag, const float* obs, int64_t num_envs, int32_
     DSParams p{obs, frag, q_out, nullptr, num_envs, num_elements, 1, 0, nullptr, nullptr, nullptr, nullptr, actions_out,
                masks};
     ds_forward_launch<2>(p, (hipStream_t)stream);
+    return check_launch();
+}
+
+int lb_ds_sample(const float* frag, const float* obs, int64_t num_envs, int32_t num_elements, const uint8_t* masks,
+                 const float* uniforms, float* logits_out, int32_t* actions_out, float* actions_f32_out,
+                 float* logprob_out, float* value_out, void* stream) {
+    if (!frag || !obs || !uniforms || !actions_out || !logprob_out || num_envs < 1)
+        return fail("lb_ds_sample: frag/obs/uniforms/actions_out/logprob_out NULL or num_envs < 1");
+    if (num_elements < 1 || num_elements > LB_DS_MAX_ELEMENTS_FWD)
+        return fail("num_elements must be in [1, 257] (LB_DS_MAX_ELEMENTS_FWD)");
+    DSParams p{obs, frag, logits_out, value_out, num_envs, num_elements, 1, value_out != nullptr,
+               nullptr, nullptr, nullptr, nullptr, actions_out, masks};
+    p.uniforms = uniforms;
+    p.actions_f32 = actions_f32_out;
+    p.logprob = logprob_out;
+    ds_forward_launch<LB_DS_FWD_SAMPLE>(p, (hipStream_t)stream);
     return check_launch();
 }
 
@@ -1166,7 +1184,9 @@ int lb_ds_train_forward(const float* frag, const float* obs, int64_t num_envs, i
 
 int lb_ds_forward_kernel(int32_t which, int64_t num_envs, int32_t num_elements, int32_t* tiles_out,
                          int32_t* sets_per_wave_out, int32_t* extra_row_out) {
-    if (which < LB_DS_FWD || which > LB_DS_FWD_PAIR) return fail("lb_ds_forward_kernel: unknown forward kind");
+    // (4 names no forward: the kinds of ABI 15 end at LB_DS_FWD_PAIR = 3, and 4 was refused there)
+    if (which < LB_DS_FWD || which > LB_DS_FWD_SAMPLE || which == LB_DS_FWD_PAIR + 1)
+        return fail("lb_ds_forward_kernel: unknown forward kind");
     if (num_envs < 1 || !tiles_out || !sets_per_wave_out || !extra_row_out)
         return fail("lb_ds_forward_kernel: num_envs < 1 or an output NULL");
     // (each forward's own bound: a call it would reject has no kernel to name)

@@ -56,6 +56,12 @@ struct DSParams {
     const uint64_t* ex_sc;
     int64_t ex_env_offset;
     uint32_t ex_key0, ex_key1;
+    // sample mode (MODE 5 = LB_DS_FWD_SAMPLE, lb_ds_sample): the categorical draw of every set by
+    // inverse CDF on uniforms[b] over its masked logits (masks above), into actions (int32),
+    // actions_f32 (the same value as float; NULL = skip) and logprob
+    const float* uniforms;
+    float* actions_f32;
+    float* logprob;
 };
 
 // lb_dqn_act's decision: true when this launch explores (the random actions are written)
@@ -284,6 +290,94 @@ __device__ __forceinline__ float from_col_dyn(float v, int s) {
         case 1: return from_col<1>(v);
         case 2: return from_col<2>(v);
         default: return from_col<3>(v);
+    }
+}
+
+// ---- sample mode (MODE 5 = LB_DS_FWD_SAMPLE, lb_ds_sample): the categorical draw in the forward ----
+// Per set b over its R masked logits l[r] = (masks == NULL || masks[b][r]) ? logit[b][r] : -1e8:
+//   m = max_r l[r], e[r] = exp(l[r] - m), c[r] = e[0] + .. + e[r] (inclusive, row order), S = c[R-1]
+//   action  = the first row with e[r] > 0 and c[r] >= u[b] S; if rounding leaves none, the last
+//             row with e[r] > 0
+//   logprob = l[action] - m - log(S)
+// A masked row has e = exp(-1e8 - m) = 0 next to a valid one, so it is never returned while the
+// set has a valid row, u = 0 included.  This is a deliberate repair of the torch formula of
+// DeepSetAgent.act (count of c[r] < u S), which returns row 0 at u = 0 whether it is valid or
+// not.  A set with no valid row has every l equal and samples uniformly over all its rows, as the
+// torch formula does.  exp is exp2 on the scaled argument (e <= 1 <= S: a few ulp absolute).
+constexpr float DS_LOG2E = 1.4426950408889634f;
+template <int N>
+__device__ __forceinline__ float dpp_shr0(float v) {  // row_shr:N, 0 shifted in at the row's start
+    return __builtin_bit_cast(float,
+                              __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x110 + N, 0xf, 0xf, true));
+}
+// inclusive prefix sum over the 16 lanes of a row, in column order
+__device__ __forceinline__ float row_scan(float v) {
+    v += dpp_shr0<1>(v);
+    v += dpp_shr0<2>(v);
+    v += dpp_shr0<4>(v);
+    v += dpp_shr0<8>(v);
+    return v;
+}
+__device__ __forceinline__ float ds_read_lane(float v, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+// a wave-uniform 64-bit value as scalars: the sample mode's addresses (masks, uniforms, the
+// outputs) are then scalar bases, not loop-invariant per-lane pointers held in VGPRs (with the
+// wave's index read as a scalar in ds_fwd_body; either alone left <1, 2, 5> 12 bytes of scratch)
+__device__ __forceinline__ int64_t ds_uniform(int64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// lg[s * TS + t]: env env0 + s's masked logit of row 16 t + col (every row group holds a copy),
+// -inf past R.  The scan of a tile is row_scan plus the earlier tiles' total; the lane of row
+// group 0 that holds the action's row writes the set's outputs.
+template <int TS, int P>
+__device__ __forceinline__ void ds_sample_group(const DSParams& p, const float (&lg)[P * TS], int64_t env0, int col,
+                                                int grp) {
+    env0 = ds_uniform(env0);
+    float m[P];
+#pragma unroll
+    for (int s = 0; s < P; ++s) {
+        float v = lg[s * TS];
+#pragma unroll
+        for (int t = 1; t < TS; ++t) v = max2(v, lg[s * TS + t]);
+        m[s] = v;
+    }
+    row_reduce<true>(m);
+    float S[P], fl[2 * P];  // fl: -(first row reaching u S), the last row with e > 0
+#pragma unroll
+    for (int s = 0; s < P; ++s) {
+        float e[TS], c[TS], run = 0.f;
+#pragma unroll
+        for (int t = 0; t < TS; ++t) {
+            e[t] = __builtin_amdgcn_exp2f((lg[s * TS + t] - m[s]) * DS_LOG2E);
+            c[t] = run + row_scan(e[t]);
+            run = from_col<15>(c[t]);
+        }
+        S[s] = run;
+        const float thr = (env0 + s < p.B ? p.uniforms[env0 + s] : 0.f) * run;
+        float first = 1e9f, last = -1.f;
+#pragma unroll
+        for (int t = TS - 1; t >= 0; --t) {
+            const float row = (float)(16 * t + col);
+            if (e[t] > 0.f && c[t] >= thr) first = row;
+            if (e[t] > 0.f && last < 0.f) last = row;
+        }
+        fl[2 * s] = -first;
+        fl[2 * s + 1] = last;
+    }
+    row_reduce<true>(fl);
+#pragma unroll
+    for (int s = 0; s < P; ++s) {
+        const int a = fl[2 * s] > -1e8f ? (int)(-fl[2 * s]) : (int)fl[2 * s + 1];
+        if (grp != 0 || col != (a & 15) || env0 + s >= p.B) continue;
+        float la = lg[s * TS];
+#pragma unroll
+        for (int t = 1; t < TS; ++t) la = (a >> 4) == t ? lg[s * TS + t] : la;
+        p.actions[env0 + s] = a;
+        if (p.actions_f32) p.actions_f32[env0 + s] = (float)a;
+        p.logprob[env0 + s] = (la - m[s]) - logf(S[s]);
     }
 }
 
@@ -536,7 +630,7 @@ template <int TS, int P, int MODE, bool VG = DSGeom<TS, P, MODE>::VG, bool XR = 
 __device__ __forceinline__ int32_t ds_group_actor(const DSParams& p, const float* W, int lane, int64_t env0, int col,
                                                   int grp, int R, const float (&h0)[P * TS][2], const float (&m0)[2],
                                                   float* xs = nullptr, const float* xr0 = nullptr) {
-    constexpr bool TRAIN = MODE == 1, ARGMAX = MODE == 2;
+    constexpr bool TRAIN = MODE == 1, ARGMAX = MODE == 2, SAMPLE = MODE == LB_DS_FWD_SAMPLE;
     constexpr int A1L = VG ? VG_A1L : DS_A1L, A1G = VG ? VG_A1G : DS_A1G, A2L = VG ? VG_A2L : DS_A2L,
                   A2G = VG ? VG_A2G : DS_A2G;
     int32_t act = -1;
@@ -587,6 +681,7 @@ __device__ __forceinline__ int32_t ds_group_actor(const DSParams& p, const float
             if (lane == 0 && env0 < p.B && p.logits) p.logits[env0 * R + R - 1] = gl + v[0];
         }
         float best[P], brow[P];  // this lane's first masked maximum per env (argmax mode)
+        float lg[P * TS];        // this lane's masked logits (sample mode)
 #pragma unroll
         for (int s = 0; s < P; ++s) {
             const float init = from_col_dyn<P>(gl, s);
@@ -602,6 +697,10 @@ __device__ __forceinline__ int32_t ds_group_actor(const DSParams& p, const float
                 const int row = 16 * t + col;
                 const bool live = row < R && env0 + s < p.B;
                 if (grp == 0 && live && p.logits) p.logits[(env0 + s) * R + row] = init + v;
+                if constexpr (SAMPLE)  // (a dead env's rows: any finite value, nothing is written)
+                    lg[s * TS + t] = row >= R ? -INFINITY
+                                     : (!live || !p.masks || p.masks[ds_uniform((env0 + s) * R) + row]) ? init + v
+                                                                                                        : -1e8f;
                 if (ARGMAX && live) {
                     const float q = (!p.masks || p.masks[(env0 + s) * R + row]) ? init + v : -1e8f;
                     if (q > best[s]) {
@@ -628,12 +727,14 @@ __device__ __forceinline__ int32_t ds_group_actor(const DSParams& p, const float
                 act = (int32_t)r;
             }
         }
+        if constexpr (SAMPLE) ds_sample_group<TS, P>(p, lg, env0, col, grp);
     }
     return act;
 }
 
 // MODE 0: logits / value; 1: training forward (TRAIN: activations, psi mean); 2: Q values
-// and the masked greedy action (ARGMAX; actor only)
+// and the masked greedy action (ARGMAX; actor only); 5: MODE 0 and the sampled action with its
+// log-probability (SAMPLE: ds_sample_group; the same image regions and LDS as MODE 0)
 // the forward of the blocks blk = 0 .. nblk - 1 (k_deepsets_fwd: the whole grid; k_ds_fwd_pair:
 // its half of the grid), W the block's LDS weight region
 template <int TS, int P, int MODE, bool XR = false>
@@ -655,7 +756,10 @@ __device__ __forceinline__ void ds_fwd_body(const DSParams& p, float* W, int blk
     const int lane = threadIdx.x & 63;
     // wave-major numbering: a batch of fewer groups than waves puts one wave on each SIMD
     // of every CU (waves 0-3 of a block sit on its 4 SIMDs) before any SIMD takes a second
-    const int64_t wave = (int64_t)(threadIdx.x >> 6) * nblk + blk;
+    // (sample mode: the wave's index as a scalar, so the addresses of its per-set inputs and
+    // outputs are scalar bases and no loop-invariant per-lane pointer is kept in VGPRs)
+    const int wv = MODE == LB_DS_FWD_SAMPLE ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
+    const int64_t wave = (int64_t)wv * nblk + blk;
     const int64_t nwaves = (int64_t)nblk * (DS_BLOCK / 64);
     const int R = p.R;
     const int col = lane & 15, grp = lane >> 4;
@@ -910,11 +1014,59 @@ __device__ __forceinline__ void store_rows_chunk(float* plane, const float (&h)[
     }
 }
 
+// sample mode of the chunked forward (ds_sample_group's definition): lg[j] is the masked logit
+// of row 64 j + lane (-inf past R).  The scan of a slot is row_scan over each 16-lane row, plus
+// the totals of the rows before it and of the slots before it; the lane holding the action's
+// row writes the set's outputs.
+constexpr int DS_SLOTS = (LB_DS_MAX_ELEMENTS_FWD + 63) / 64;
+__device__ __forceinline__ float ds_wave_max(float v) {
+    float a[1] = {v};
+    row_reduce<true>(a);
+    a[0] = max2(a[0], __shfl_xor(a[0], 16));
+    return max2(a[0], __shfl_xor(a[0], 32));
+}
+__device__ __forceinline__ void ds_sample_wave(const DSParams& p, const float (&lg)[DS_SLOTS], int64_t env, int lane) {
+    const int grp = lane >> 4;
+    float m = lg[0];
+#pragma unroll
+    for (int j = 1; j < DS_SLOTS; ++j) m = max2(m, lg[j]);
+    m = ds_wave_max(m);
+    float e[DS_SLOTS], c[DS_SLOTS], run = 0.f;
+#pragma unroll
+    for (int j = 0; j < DS_SLOTS; ++j) {
+        e[j] = __builtin_amdgcn_exp2f((lg[j] - m) * DS_LOG2E);
+        const float sc = row_scan(e[j]);
+        const float t0 = ds_read_lane(sc, 15), t1 = ds_read_lane(sc, 31), t2 = ds_read_lane(sc, 47),
+                    t3 = ds_read_lane(sc, 63);
+        const float before = grp == 0 ? 0.f : (grp == 1 ? t0 : (grp == 2 ? t0 + t1 : (t0 + t1) + t2));
+        c[j] = run + (before + sc);
+        run = run + (((t0 + t1) + t2) + t3);
+    }
+    const float thr = p.uniforms[env] * run;
+    float first = 1e9f, last = -1.f;
+#pragma unroll
+    for (int j = DS_SLOTS - 1; j >= 0; --j) {
+        const float row = (float)(64 * j + lane);
+        if (e[j] > 0.f && c[j] >= thr) first = row;
+        if (e[j] > 0.f && last < 0.f) last = row;
+    }
+    const float f = -ds_wave_max(-first), l = ds_wave_max(last);
+    const int a = f < 1e8f ? (int)f : (int)l;
+    if (lane != (a & 63)) return;
+    float la = lg[0];
+#pragma unroll
+    for (int j = 1; j < DS_SLOTS; ++j) la = (a >> 6) == j ? lg[j] : la;
+    p.actions[env] = a;
+    if (p.actions_f32) p.actions_f32[env] = (float)a;
+    p.logprob[env] = (la - m) - logf(run);
+}
+
 // MODE 0: logits / value; 1: training forward (activations, set maxima + first argmax rows,
-// psi mean; as k_deepsets_fwd<.., 1>); 2: Q values and the masked greedy action (actor only)
+// psi mean; as k_deepsets_fwd<.., 1>); 2: Q values and the masked greedy action (actor only);
+// 5: MODE 0 and the sampled action with its log-probability (ds_sample_wave)
 template <int MODE>
 __global__ __launch_bounds__(DS_BLOCK, 2) void k_deepsets_fwd_big(DSParams p) {
-    constexpr bool ARGMAX = MODE == 2, TRAIN = MODE == 1;
+    constexpr bool ARGMAX = MODE == 2, TRAIN = MODE == 1, SAMPLE = MODE == LB_DS_FWD_SAMPLE;
     if (ARGMAX && p.ex_on && ds_dqn_explore(p)) return;
     __shared__ __attribute__((aligned(16))) float W[DS_LDS_FLOATS];
     const int nstage = (ARGMAX || !p.critic) ? DS_C1L : DS_FLOATS;
@@ -984,6 +1136,11 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_deepsets_fwd_big(DSParams p) {
             gl += __shfl_xor(gl, 16);
             gl += __shfl_xor(gl, 32);
             float best = -INFINITY, brow = 1e9f;
+            // sample mode: the set's masked logits stay in registers for the draw, lane l keeps
+            // rows l, 64 + l, .. (row 32 c + 16 t + col is lane (col, 2 (c & 1) + t)'s slot c >> 1)
+            float lgr[DS_SLOTS];
+#pragma unroll
+            for (int j = 0; j < DS_SLOTS; ++j) lgr[j] = -INFINITY;
             for (int c = 0; c < nch; ++c) {
                 uint32_t wo = 0;
                 asm volatile("" : "+s"(wo));
@@ -1005,6 +1162,11 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_deepsets_fwd_big(DSParams p) {
                     const int row = 16 * DS_CT * c + 16 * t + col;
                     if (row >= R) continue;
                     if (grp == 0 && p.logits) p.logits[env * R + row] = gl + v;
+                    if (SAMPLE && grp == 2 * (c & 1) + t) {
+                        const float q = (!p.masks || p.masks[env * R + row]) ? gl + v : -1e8f;
+#pragma unroll
+                        for (int j = 0; j < DS_SLOTS; ++j) lgr[j] = j == (c >> 1) ? q : lgr[j];
+                    }
                     if (ARGMAX) {
                         const float q = (!p.masks || p.masks[env * R + row]) ? gl + v : -1e8f;
                         if (q > best) {  // rows ascend: the first maximum of this lane wins
@@ -1021,6 +1183,7 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_deepsets_fwd_big(DSParams p) {
                 row_reduce<true>(cc);
                 if (lane == 0) p.actions[env] = (int32_t)(-cc[0]);
             }
+            if (SAMPLE) ds_sample_wave(p, lgr, env, lane);
         }
         if (ARGMAX || !p.critic) continue;
         // critic: the max of c1, then the max and the sum of c2, then layer 3 / rho as above

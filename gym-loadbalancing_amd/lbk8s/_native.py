@@ -16,13 +16,13 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 SOURCES = ("lbk8s.hip", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
            "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_dqn.h", "../../include/lbk8s.h", "lbk8s_lean_launch.h",
            "lbk8s_lean_inst.hip", "lbk8s_build.cpp")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 LB_REWARD = {"naive": 0, "latency": 1, "fairness": 2, "multi": 3}
 LB_RNG_PHILOX, LB_RNG_TRACE = 0, 1
 LB_POLICY = {"topo": 0, "zone_cpu": 1, "endpoint_cpu": 2, "random": 3}
 # lb_ds_forward_kernel's `which` (include/lbk8s.h LB_DS_FWD*)
-LB_DS_FWD, LB_DS_FWD_TRAIN, LB_DS_FWD_ARGMAX, LB_DS_FWD_PAIR = 0, 1, 2, 3
+LB_DS_FWD, LB_DS_FWD_TRAIN, LB_DS_FWD_ARGMAX, LB_DS_FWD_PAIR, LB_DS_FWD_SAMPLE = 0, 1, 2, 3, 5
 # lb_rollout_kernel's answers (include/lbk8s.h LB_ROLLOUT_*)
 LB_ROLLOUT = {0: "k_rollout_lean", 1: "k_rollout_img", 2: "k_rollout_tpe", 3: "policy+step launches",
               4: "k_rollout_slice", 5: "k_rollout_lean_split"}
@@ -208,6 +208,7 @@ def lib():
     L.lb_ds_pack.argtypes = [C.POINTER(LBDSWeightsC), vp, vp]
     L.lb_ds_forward.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.lb_ds_q_argmax.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
+    L.lb_ds_sample.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     f32 = C.c_float
     L.lb_ppo_head.argtypes = [vp] * 8 + [i64, i32, f32, f32, f32, i32, vp, vp, vp, vp]
     L.lb_replay_add.argtypes = [i64, i32, i64] + [vp] * 15 + [vp]
@@ -236,7 +237,7 @@ def lib():
               "lb_replay_add", "lb_ppo_head", "lb_episode_log", "lb_dqn_act", "lb_dqn_head",
               "lb_replay_sample", "lb_ds_set_grads", "lb_dqn_step", "lb_dqn_steps",
               "lb_dqn_steps_supported", "lb_ds_pack_pair", "lb_ds_forward_pair", "lb_ds_over_sets",
-              "lb_ds_train_backward_sets", "lb_ds_forward_kernel"):
+              "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample"):
         getattr(L, f).restype = C.c_int
     v = L.lb_abi_version()
     if v != ABI_VERSION and product:
@@ -274,4 +275,4 @@ EXPORTED_SYMBOLS = ("lb_abi_version", "lb_last_error", "lb_validate_config", "lb
                     "lb_rollout_kernel", "lb_source_hash", "lb_build_flags", "lb_build_compiler", "lb_reward64",
                     "lb_dqn_step",
                     "lb_dqn_steps", "lb_dqn_steps_supported", "lb_ds_pack_pair", "lb_ds_forward_pair",
-                    "lb_ds_over_sets", "lb_ds_train_backward_sets", "lb_ds_forward_kernel")
+                    "lb_ds_over_sets", "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample")

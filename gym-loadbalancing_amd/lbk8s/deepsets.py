@@ -163,11 +163,20 @@ class DeepSetAgent(nn.Module):
         return action, dist.log_prob(action), dist.entropy(), value
 
     @torch.no_grad()
-    def act(self, x, masks=None, generator=None, uniforms=None):
+    def act(self, x, masks=None, generator=None, uniforms=None, out=None):
         """Rollout step: (action, log_prob, value) with no autograd graph.  `uniforms` (B,)
         U(0,1) draws: the categorical sample by inverse CDF on them (no RNG call inside, so
-        the step can be captured in a HIP graph); otherwise torch.multinomial."""
+        the step can be captured in a HIP graph); otherwise torch.multinomial.
+
+        `out`: a dict of the caller's tensors, fused.deepsets_sample's keyword arguments
+        (actions_out, logprob_out, value_out; optionally actions_f32_out, logits_out).  With
+        `uniforms` and where the fused path covers the input, the whole step is then one launch
+        that writes them, and the returned tensors are views of `out` (the action int32).  That
+        path never draws an invalid row while a valid one exists, u = 0 included, where the
+        formula below returns row 0.  Every other call is the code below, unchanged."""
         from . import fused
+        if out is not None and uniforms is not None and fused.sample_supported(self, x):
+            return fused.deepsets_sample(self, x, uniforms, masks, **out)
         logits, value = fused.deepsets_forward(self, x)
         lg = masked_logits(logits, masks)
         logp_all = torch.log_softmax(lg, dim=-1)

@@ -109,6 +109,7 @@ def _launch(frag, x, logits, value):
 
 FWD, FWD_TRAIN, FWD_ARGMAX, FWD_PAIR = (_native.LB_DS_FWD, _native.LB_DS_FWD_TRAIN, _native.LB_DS_FWD_ARGMAX,
                                         _native.LB_DS_FWD_PAIR)
+FWD_SAMPLE = _native.LB_DS_FWD_SAMPLE  # deepsets_sample (lb_ds_sample): FWD's variant for every geometry
 
 
 def forward_kernel(which, B, R):
@@ -138,6 +139,59 @@ def deepsets_forward(agent, x: torch.Tensor, require: bool = False):
     value = torch.empty((B,), dtype=torch.float32, device=x.device)
     _launch(frag, x, logits, value)
     return logits, value
+
+
+def sample_supported(agent, x) -> bool:
+    """Whether deepsets_sample covers (agent, x): deepsets_forward's rule."""
+    return bool(ENABLED and _geometry_ok(agent.actor.net, x))
+
+
+def _sample_out(name, t, shape, dtype, device, optional=False):
+    if t is None:
+        if optional:
+            return None
+        raise ValueError(f"deepsets_sample: {name} is required")
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()
+            or t.device != device):
+        raise ValueError(f"deepsets_sample: {name} must be a contiguous {shape} {dtype} tensor on {device}")
+    return t
+
+
+@torch.no_grad()
+def deepsets_sample(agent, x: torch.Tensor, uniforms: torch.Tensor, masks=None, *, actions_out, logprob_out,
+                    value_out, actions_f32_out=None, logits_out=None):
+    """The stochastic rollout step of a DeepSetAgent in one launch (lb_ds_sample): the logits and
+    the value of deepsets_forward (bit for bit) and, per set, the categorical sample by inverse
+    CDF on uniforms (B,) in [0, 1) over the masked logits, its log-probability and the value,
+    written straight into the caller's tensors -- a rollout storage row (`logprobs[step]`) can
+    be passed as it is.  An invalid row is never drawn while the set has a valid one (u = 0
+    included; DeepSetAgent.act's torch formula returns row 0 there).
+
+    x (B, R, 8) float32 contiguous; masks (B, R) bool or None; actions_out (B,) int32;
+    logprob_out, value_out and actions_f32_out (B,) float32 (the action as float, optional);
+    logits_out (B, R) float32 (optional).  No allocation and no host synchronisation: the
+    call can be captured in a HIP graph (the cached weight image must then stay valid: `pin`,
+    or no parameter update between capture and replay).  Returns (actions_out, logprob_out,
+    value_out)."""
+    if not sample_supported(agent, x):
+        raise RuntimeError(f"fused deep-sets sampling does not cover input {tuple(x.shape)} on {x.device}")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("deepsets_sample: x must be a contiguous float32 tensor")
+    B, R, _ = x.shape
+    dev = x.device
+    _sample_out("uniforms", uniforms, (B,), torch.float32, dev)
+    _sample_out("masks", masks, (B, R), torch.bool, dev, optional=True)
+    _sample_out("actions_out", actions_out, (B,), torch.int32, dev)
+    _sample_out("logprob_out", logprob_out, (B,), torch.float32, dev)
+    _sample_out("value_out", value_out, (B,), torch.float32, dev)
+    _sample_out("actions_f32_out", actions_f32_out, (B,), torch.float32, dev, optional=True)
+    _sample_out("logits_out", logits_out, (B, R), torch.float32, dev, optional=True)
+    frag = packed(agent, agent.actor.net, agent.critic)
+    _native.check(_native.lib().lb_ds_sample(
+        frag.data_ptr(), x.data_ptr(), B, R, _ptr(masks), uniforms.data_ptr(), _ptr(logits_out),
+        actions_out.data_ptr(), _ptr(actions_f32_out), logprob_out.data_ptr(), value_out.data_ptr(),
+        torch.cuda.current_stream(dev).cuda_stream))
+    return actions_out, logprob_out, value_out
 
 
 @torch.no_grad()

@@ -99,7 +99,12 @@ class PPO_DeepSets:
                  update_epochs: int = 4, norm_adv: bool = True, clip_coef: float = 0.2,
                  clip_vloss: bool = True, ent_coef: float = 0.01, vf_coef: float = 0.5,
                  max_grad_norm: float = 0.5, target_kl: Optional[float] = None, seed: int = 1,
-                 device=None, log_fn=None, num_envs=None, tensorboard_log=None, use_graphs=None):
+                 device=None, log_fn=None, num_envs=None, tensorboard_log=None, use_graphs=None,
+                 fused_act: bool = False):
+        # fused_act: the rollout's policy step as ONE launch (fused.deepsets_sample) that writes the
+        # env's action buffer and the step's storage rows (actions, logprobs, values) directly.  Off
+        # by default: a draw on a CDF boundary can pick the neighbouring row (and u = 0 never picks
+        # an invalid one), which changes learner trajectories.
         # num_envs / tensorboard_log: accepted for signature compatibility with
         # ppo_deepset.py:53-75 (the env's num_envs is used; there is no tensorboard writer)
         self.env = env
@@ -156,6 +161,7 @@ class PPO_DeepSets:
         # step).  Capturing the T steps as one HIP graph was measured (config 4: 19.5 ms per
         # rollout either way): the rollout is GPU-bound, so it runs eagerly.
         self._u = torch.zeros((T, B), device=dev)
+        self.fused_act = bool(fused_act) and fused.sample_supported(self.agent, self.obs[0])
 
     def _rollout_body(self, next_done):
         """The T vector steps on the storage buffers (no host sync, no RNG call: the uniforms
@@ -165,11 +171,16 @@ class PPO_DeepSets:
         next_obs = self.obs[0]
         for step in range(T):
             self.dones[step] = next_done
-            action, logprob, value = self.agent.act(next_obs, uniforms=self._u[step])  # no masks (:169)
-            self.values[step] = value
-            self.actions[step] = action.float()
-            self.logprobs[step] = logprob
-            self._act.copy_(action)
+            if self.fused_act:  # one launch: the sample and its storage rows (no masks, :169)
+                self.agent.act(next_obs, uniforms=self._u[step],
+                               out=dict(actions_out=self._act, actions_f32_out=self.actions[step],
+                                        logprob_out=self.logprobs[step], value_out=self.values[step]))
+            else:
+                action, logprob, value = self.agent.act(next_obs, uniforms=self._u[step])  # no masks (:169)
+                self.values[step] = value
+                self.actions[step] = action.float()
+                self.logprobs[step] = logprob
+                self._act.copy_(action)
             # the env writes the next observation straight into the next storage slot
             next_obs = self.obs[step + 1] if step + 1 < T else self._last_obs
             env.step_device(self._act, obs_out=next_obs, reward_out=self.rewards[step], done_out=self._done_u8)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LBK8S_ABI_VERSION 15
+#define LBK8S_ABI_VERSION 16
 
 /* reward_function names of loadbalancer_k8s_env.py:20-31 */
 enum { LB_REWARD_NAIVE = 0, LB_REWARD_LATENCY = 1, LB_REWARD_FAIRNESS = 2, LB_REWARD_MULTI = 3 };
@@ -269,6 +269,29 @@ int lb_ds_forward(const float* frag, const float* obs, int64_t num_envs, int32_t
 int lb_ds_q_argmax(const float* frag, const float* obs, int64_t num_envs, int32_t num_elements,
                    const uint8_t* masks, float* q_out, int32_t* actions_out, void* stream);
 
+/* (ABI 16) The stochastic policy's rollout step (envs/ppo_deepset.py:161-172,
+ * deep_sets_agent_original.py:131-145) in one launch: lb_ds_forward's logits and value (the same
+ * kernel variant, bit for bit) and, per set b, the categorical sample by inverse CDF on
+ * uniforms[b] in [0, 1) over its R masked logits
+ *   l[r] = (masks == NULL || masks[b][r]) ? logit[b][r] : -1e8
+ *   m = max_r l[r],  e[r] = exp(l[r] - m),  c[r] = e[0] + .. + e[r] (f32, row order),  S = c[R-1]
+ *   action  = the first row r with e[r] > 0 and c[r] >= uniforms[b] * S; if rounding leaves
+ *             none, the last row with e[r] > 0
+ *   logprob = l[action] - m - log(S)
+ * A row with mask 0 is never returned while the set has a valid row, uniforms[b] == 0 included:
+ * a deliberate repair of the torch formula (DeepSetAgent.act: the count of c[r] < u S), which
+ * returns row 0 there whether it is valid or not.  A set with no valid row has every l equal
+ * and samples uniformly over all its rows, as the torch formula does.
+ * masks [B,R] u8 or NULL (all valid); uniforms [B] f32.  Outputs, each written once:
+ * actions_out [B] i32, actions_f32_out [B] f32 (the same value as float: PPO's storage;
+ * NULL = skip), logprob_out [B] f32, value_out [B] f32 (NULL = an actor-only image, no critic
+ * evaluated), logits_out [B,R] f32 (unmasked; NULL = skip).  1 <= R <= LB_DS_MAX_ELEMENTS_FWD.
+ * No host synchronisation, allocation or atomics: capturable in a HIP graph. */
+int lb_ds_sample(const float* frag, const float* obs, int64_t num_envs, int32_t num_elements,
+                 const uint8_t* masks, const float* uniforms, float* logits_out,
+                 int32_t* actions_out, float* actions_f32_out, float* logprob_out,
+                 float* value_out, void* stream);
+
 /* GPU-resident replay add (dqn_deepset.py:158-174, SB3 ReplayBuffer layout [slots][B]...)
  * plus obs <- next_obs and per-env finished-episode sums, in one launch.  The slot is
  * *pos_in (device); (pos + 1) % slots is written to *pos_out, which must be a different
@@ -432,10 +455,12 @@ int lb_ds_forward_pair(const float* frag_a, const float* obs_a, float* logits_a,
 
 /* (ABI 15) Which forward kernel a call takes on the current device; host only, no launch:
  * lb_ds_forward (LB_DS_FWD), lb_ds_train_forward (LB_DS_FWD_TRAIN), lb_ds_q_argmax / lb_dqn_act
- * (LB_DS_FWD_ARGMAX) or lb_ds_forward_pair (LB_DS_FWD_PAIR) of num_envs sets of num_elements
+ * (LB_DS_FWD_ARGMAX), lb_ds_forward_pair (LB_DS_FWD_PAIR) or lb_ds_sample (LB_DS_FWD_SAMPLE,
+ * ABI 16: LB_DS_FWD's variant for every geometry; 4 names no forward and stays refused, as in
+ * ABI 15) of num_envs sets of num_elements
  * rows.  The launchers take their choice from the same rule (it weighs num_envs against the
  * device's CU count).  Refuses a set size the named forward refuses. */
-enum { LB_DS_FWD = 0, LB_DS_FWD_TRAIN = 1, LB_DS_FWD_ARGMAX = 2, LB_DS_FWD_PAIR = 3 };
+enum { LB_DS_FWD = 0, LB_DS_FWD_TRAIN = 1, LB_DS_FWD_ARGMAX = 2, LB_DS_FWD_PAIR = 3, LB_DS_FWD_SAMPLE = 5 };
 int lb_ds_forward_kernel(int32_t which, int64_t num_envs, int32_t num_elements,
                          int32_t* tiles_out,          /* TS 1..5; 0 = the chunked kernel (R > 80) */
                          int32_t* sets_per_wave_out,  /* P */

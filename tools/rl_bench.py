@@ -43,6 +43,9 @@ def parse():
     ap.add_argument("--torch-set-sums", action="store_true",
                     help="A/B reference: the training step's sums over the sets as round-5's chunked torch GEMMs "
                          "(fused_train._over_sets) instead of lb_ds_over_sets")
+    ap.add_argument("--fused-act", action="store_true",
+                    help="PPO: the rollout's policy step as one launch (PPO_DeepSets(fused_act=True): lb_ds_sample "
+                         "writes the action and the storage rows)")
     return ap.parse_args()
 
 
@@ -90,7 +93,8 @@ def main():
     if args.algo == "ppo":
         from lbk8s.ppo import PPO_DeepSets
         ppo = PPO_DeepSets(env, num_steps=args.num_steps, n_minibatches=8, update_epochs=4, ent_coef=0.001,
-                           gamma=0.95, gae_lambda=0.97, seed=1, device=dev)
+                           gamma=0.95, gae_lambda=0.97, seed=1, device=dev, fused_act=args.fused_act)
+        out.update(fused_act=ppo.fused_act)
         next_obs = env.reset()
         next_done = torch.zeros(B, device=dev)
         for _ in range(args.warmup_updates):
@@ -115,6 +119,7 @@ def main():
                    unit="env-steps/s", updates=args.updates, num_steps=args.num_steps, minibatches=8, epochs=4,
                    ms_per_update=wall / args.updates * 1e3, rollout_ms=t_roll / args.updates * 1e3,
                    update_ms=t_upd / args.updates * 1e3,
+                   rollout_us_per_vector_step=t_roll / (args.updates * args.num_steps) * 1e6,
                    rollout_env_steps_per_s=args.num_steps * B * world * args.updates / max_over_ranks(t_roll),
                    last=dict((k, round(v, 6)) for k, v in stats.items()),
                    ep_return=ppo.episode_returns[-1] if ppo.episode_returns else None)
