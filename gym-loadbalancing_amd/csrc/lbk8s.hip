@@ -142,8 +142,8 @@ struct EpLogParams {
     uint32_t* count;
 };
 
-__global__ __launch_bounds__(256) void k_episode_log(EpLogParams p) {
-    const int64_t env = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// one env's part of the episode log; every lane of the wave calls it (the ballot), live or not
+__device__ __forceinline__ void episode_log_env(const EpLogParams& p, int64_t env) {
     const int lane = threadIdx.x & 63;
     const bool live = env < p.B;
     bool d = false;
@@ -172,6 +172,90 @@ __global__ __launch_bounds__(256) void k_episode_log(EpLogParams p) {
     row[LB_EPLOG_ACTION] = (double)p.actions[env];
     row[LB_EPLOG_ENV] = (double)env;
     row[LB_EPLOG_TAG] = (double)p.tag;
+}
+
+__global__ __launch_bounds__(256) void k_episode_log(EpLogParams p) {
+    episode_log_env(p, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// lb_ppo_record: the PPO vector step's bookkeeping in one launch (ppo_deepset.py:174-190: the
+// next step's done row as float32, the finished episodes' returns) and, with a log, lb_episode_log.
+// The sums are per env, as lb_replay_add's: deterministic, reduced once per rollout by the caller.
+struct PPORecordParams {
+    EpLogParams log;  // log.log == NULL: no episode log; B, done and ep_stats are always set
+    float* next_done;
+    double* ep_sum;  // [B] or NULL (then ep_cnt too)
+    double* ep_cnt;
+};
+
+__global__ __launch_bounds__(256) void k_ppo_record(PPORecordParams p) {
+    const int64_t env = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (env < p.log.B) {
+        const bool d = p.log.done[env] != 0;
+        p.next_done[env] = d ? 1.f : 0.f;
+        if (d && p.ep_sum) {
+            p.ep_sum[env] += p.log.ep_stats[env * LB_ST_K + LB_ST_RETURN];
+            p.ep_cnt[env] += 1.0;
+        }
+    }
+    if (p.log.log) episode_log_env(p.log, env);  // (wave-uniform: every lane takes part in its ballot)
+}
+
+// lb_gae: the GAE recurrence (ppo_deepset.py:192-205) of one env per thread, t downwards with
+// values[t + 1] / dones[t + 1] carried in registers, so every input word is read once, coalesced
+// across envs.  float32 op for op as torch evaluates it (the build has -ffp-contract=off).  The
+// loads of GAE_UNROLL steps are issued before the chain that consumes them: their addresses do
+// not depend on the recurrence.
+constexpr int GAE_BLOCK = 64;  // small blocks: PPO's 4096 envs spread over 64 CUs
+constexpr int GAE_UNROLL = 4;
+struct GAEParams {
+    const float* rewards;
+    const float* values;
+    const float* dones;
+    const float* next_value;
+    const float* next_done;
+    int64_t T, B;
+    float g, gl;  // (float)gamma, (float)(gamma * gae_lambda)
+    float* adv;
+    float* ret;
+};
+
+__device__ __forceinline__ void gae_step(const GAEParams& p, float r, float v, float& nv, float& nd, float& last,
+                                         int64_t idx) {
+    const float nnt = 1.f - nd;
+    const float delta = (r + (p.g * nv) * nnt) - v;
+    last = delta + (p.gl * nnt) * last;
+    p.adv[idx] = last;
+    p.ret[idx] = last + v;
+    nv = v;
+}
+
+__global__ __launch_bounds__(GAE_BLOCK) void k_gae(GAEParams p) {
+    const int64_t b = (int64_t)blockIdx.x * GAE_BLOCK + threadIdx.x;
+    if (b >= p.B) return;
+    float nv = p.next_value[b], nd = p.next_done[b], last = 0.f;
+    int64_t t = p.T - 1;
+    for (; t >= GAE_UNROLL - 1; t -= GAE_UNROLL) {
+        float r[GAE_UNROLL], v[GAE_UNROLL], d[GAE_UNROLL];
+#pragma unroll
+        for (int k = 0; k < GAE_UNROLL; ++k) {
+            const int64_t idx = (t - k) * p.B + b;
+            r[k] = p.rewards[idx];
+            v[k] = p.values[idx];
+            d[k] = p.dones[idx];
+        }
+#pragma unroll
+        for (int k = 0; k < GAE_UNROLL; ++k) {
+            gae_step(p, r[k], v[k], nv, nd, last, (t - k) * p.B + b);
+            nd = d[k];
+        }
+    }
+    for (; t >= 0; --t) {
+        const int64_t idx = t * p.B + b;
+        const float r = p.rewards[idx], v = p.values[idx], d = p.dones[idx];
+        gae_step(p, r, v, nv, nd, last, idx);
+        nd = d;
+    }
 }
 
 // LAT[k][j]: endpoint latency after j selections from trunc(initial) = k
@@ -863,6 +947,40 @@ int lb_episode_log(int64_t num_envs, const uint8_t* done, const double* ep_stats
         return fail("episode log: buffers NULL or num_envs < 1");
     EpLogParams p{num_envs, done, ep_stats, reward, reward64, actions, ret32, ep_r32, tag, log, cap, count};
     hipLaunchKernelGGL(k_episode_log, dim3(env_blocks(num_envs)), dim3(BLOCK), 0, (hipStream_t)stream, p);
+    return check_launch();
+}
+
+int lb_ppo_record(int64_t num_envs, const uint8_t* done, const double* ep_stats, float* next_done_out,
+                  double* ep_sum, double* ep_cnt, const float* reward, const double* reward64,
+                  const int32_t* actions, float* ret32, float* ep_r32, int64_t tag, double* log, int64_t cap,
+                  uint32_t* count, void* stream) {
+    if (num_envs < 1 || !done || !ep_stats || !next_done_out)
+        return fail("lb_ppo_record: done/ep_stats/next_done_out NULL or num_envs < 1");
+    if ((ep_sum == nullptr) != (ep_cnt == nullptr)) return fail("lb_ppo_record: ep_sum and ep_cnt go together");
+    if (log && (!reward || !actions || !ret32 || !count || cap < 0))
+        return fail("lb_ppo_record: a log needs reward, actions, ret32, count and cap >= 0");
+    PPORecordParams p{{num_envs, done, ep_stats, reward, reward64, actions, ret32, ep_r32, tag, log, cap, count},
+                      next_done_out, ep_sum, ep_cnt};
+    hipLaunchKernelGGL(k_ppo_record, dim3(env_blocks(num_envs)), dim3(BLOCK), 0, (hipStream_t)stream, p);
+    return check_launch();
+}
+
+int lb_gae(const float* rewards, const float* values, const float* dones, const float* next_value,
+           const float* next_done, int64_t num_steps, int64_t num_envs, double gamma, double gae_lambda,
+           float* advantages_out, float* returns_out, void* stream) {
+    if (num_steps < 1 || num_envs < 1) return fail("lb_gae: num_steps < 1 or num_envs < 1");
+    if (!rewards || !values || !dones || !next_value || !next_done || !advantages_out || !returns_out)
+        return fail("lb_gae: a buffer is NULL");
+    const void* in[5] = {rewards, values, dones, next_value, next_done};
+    for (const void* q : in)
+        if (q == advantages_out || q == returns_out) return fail("lb_gae: an output is also an input");
+    if (advantages_out == returns_out) return fail("lb_gae: advantages_out == returns_out");
+    // rounded once, the product in double first (Python's gamma * gae_lambda)
+    GAEParams p{rewards, values, dones, next_value, next_done, num_steps, num_envs,
+                (float)gamma, (float)(gamma * gae_lambda), advantages_out, returns_out};
+    const int64_t blocks = (num_envs + GAE_BLOCK - 1) / GAE_BLOCK;
+    if (blocks > 0x7FFFFFFF) return fail("lb_gae: num_envs too large for one launch");
+    hipLaunchKernelGGL(k_gae, dim3((unsigned)blocks), dim3(GAE_BLOCK), 0, (hipStream_t)stream, p);
     return check_launch();
 }
 

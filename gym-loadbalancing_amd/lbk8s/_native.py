@@ -16,7 +16,7 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 SOURCES = ("lbk8s.hip", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
            "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_dqn.h", "../../include/lbk8s.h", "lbk8s_lean_launch.h",
            "lbk8s_lean_inst.hip", "lbk8s_build.cpp")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 LB_REWARD = {"naive": 0, "latency": 1, "fairness": 2, "multi": 3}
 LB_RNG_PHILOX, LB_RNG_TRACE = 0, 1
@@ -219,6 +219,8 @@ def lib():
     L.lb_ds_pack_pair.argtypes = [C.POINTER(LBDSWeightsC), vp, vp, vp]
     L.lb_ds_train_backward.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lb_episode_log.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp]
+    L.lb_ppo_record.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp]
+    L.lb_gae.argtypes = [vp] * 5 + [i64, i64, C.c_double, C.c_double, vp, vp, vp]
     L.lb_reward64.argtypes = [vp, cfgp, i64, C.POINTER(C.c_void_p)]
     L.lb_dqn_act.argtypes = [vp, vp, i64, i32, vp, vp, cfgp, C.POINTER(LBDQNExploreC), vp, vp]
     L.lb_dqn_step.argtypes = [vp, vp, i64, i32, vp, vp, cfgp, C.POINTER(LBDQNExploreC), vp, vp, vp, vp, vp, vp,
@@ -237,7 +239,7 @@ def lib():
               "lb_replay_add", "lb_ppo_head", "lb_episode_log", "lb_dqn_act", "lb_dqn_head",
               "lb_replay_sample", "lb_ds_set_grads", "lb_dqn_step", "lb_dqn_steps",
               "lb_dqn_steps_supported", "lb_ds_pack_pair", "lb_ds_forward_pair", "lb_ds_over_sets",
-              "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample"):
+              "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample", "lb_ppo_record", "lb_gae"):
         getattr(L, f).restype = C.c_int
     v = L.lb_abi_version()
     if v != ABI_VERSION and product:
@@ -275,4 +277,5 @@ EXPORTED_SYMBOLS = ("lb_abi_version", "lb_last_error", "lb_validate_config", "lb
                     "lb_rollout_kernel", "lb_source_hash", "lb_build_flags", "lb_build_compiler", "lb_reward64",
                     "lb_dqn_step",
                     "lb_dqn_steps", "lb_dqn_steps_supported", "lb_ds_pack_pair", "lb_ds_forward_pair",
-                    "lb_ds_over_sets", "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample")
+                    "lb_ds_over_sets", "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample",
+                    "lb_ppo_record", "lb_gae")

@@ -20,6 +20,9 @@ unpack/average + clip + Adam — with the bucket's all_reduce issued between the
 same stream (the collective stays outside the captures, so any backend works).  The
 capture's warm-up steps are undone (parameters restored, Adam state zeroed), so the graph
 path computes the same update as the eager one.
+
+With fused_act and fused_bookkeeping a rollout's vector step is three launches (lb_ds_sample,
+lb_step, lb_ppo_record) and GAE is one (lb_gae, gae_device); both flags are off by default.
 """
 import os
 import time
@@ -28,6 +31,7 @@ from typing import Optional
 import torch
 from torch import nn, optim
 
+from . import _native
 from . import dist as lbdist
 from . import fused, fused_train
 from .deepsets import DeepSetAgent
@@ -93,6 +97,47 @@ def compute_gae(rewards, values, dones, next_value, next_done, gamma, gae_lambda
     return advantages, advantages + values
 
 
+def _gae_arg(name, t, shape, device):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape
+            or not t.is_contiguous() or t.device != device):
+        raise ValueError(f"gae_device: {name} must be a contiguous {shape} torch.float32 tensor on {device}")
+    return t
+
+
+@torch.no_grad()
+def gae_device(rewards, values, dones, next_value, next_done, gamma, gae_lambda, out=None):
+    """compute_gae in one launch (lb_gae): the same recurrence in float32, op for op, one thread
+    per env -> (advantages, returns), (T, B) each.
+
+    rewards, values, dones (T, B) and next_value, next_done with B elements (next_value may be
+    (1, B), as update() shapes it): contiguous float32 tensors on one HIP device, else
+    ValueError.  out = (advantages, returns) preallocated (T, B) tensors, distinct from each
+    other and from the inputs (default: allocated here).  No host synchronisation; with `out`
+    no allocation either, so the call can be captured in a HIP graph."""
+    if not isinstance(rewards, torch.Tensor) or rewards.dim() != 2:
+        raise ValueError("gae_device: rewards must be a (T, B) tensor")
+    if rewards.device.type != "cuda":
+        raise ValueError(f"gae_device: the tensors must be on a HIP device, not {rewards.device}")
+    T, B = rewards.shape
+    dev = rewards.device
+    for name, t in (("rewards", rewards), ("values", values), ("dones", dones)):
+        _gae_arg(name, t, (T, B), dev)
+    for name, t in (("next_value", next_value), ("next_done", next_done)):
+        if isinstance(t, torch.Tensor) and tuple(t.shape) == (1, B):
+            t = t.view(B)
+        _gae_arg(name, t, (B,), dev)
+    if out is None:
+        out = (torch.empty_like(rewards), torch.empty_like(rewards))
+    adv, ret = out
+    _gae_arg("out[0]", adv, (T, B), dev)
+    _gae_arg("out[1]", ret, (T, B), dev)
+    _native.check(_native.lib().lb_gae(
+        rewards.data_ptr(), values.data_ptr(), dones.data_ptr(), next_value.data_ptr(), next_done.data_ptr(),
+        T, B, float(gamma), float(gae_lambda), adv.data_ptr(), ret.data_ptr(),
+        torch.cuda.current_stream(dev).cuda_stream))
+    return adv, ret
+
+
 class PPO_DeepSets:
     def __init__(self, env, learning_rate: float = 2.5e-4, anneal_lr: bool = False, num_steps: int = 128,
                  gae: bool = True, gae_lambda: float = 0.97, gamma: float = 0.95, n_minibatches: int = 4,
@@ -100,11 +145,16 @@ class PPO_DeepSets:
                  clip_vloss: bool = True, ent_coef: float = 0.01, vf_coef: float = 0.5,
                  max_grad_norm: float = 0.5, target_kl: Optional[float] = None, seed: int = 1,
                  device=None, log_fn=None, num_envs=None, tensorboard_log=None, use_graphs=None,
-                 fused_act: bool = False):
+                 fused_act: bool = False, fused_bookkeeping: bool = False):
         # fused_act: the rollout's policy step as ONE launch (fused.deepsets_sample) that writes the
         # env's action buffer and the step's storage rows (actions, logprobs, values) directly.  Off
         # by default: a draw on a CDF boundary can pick the neighbouring row (and u = 0 never picks
         # an invalid one), which changes learner trajectories.
+        # fused_bookkeeping: the rest of the rollout step (the done row of the storage, the finished
+        # episodes' sums, the VecMonitor log) as ONE launch (LBVecEnv.record_ppo) and GAE as one
+        # launch (gae_device) instead of eager torch arithmetic.  Same storage, advantages and
+        # monitor file, bit for bit; the logged mean return sums per-env float64 accumulators, so
+        # it can differ from the default's in the last bits.  Off by default, as fused_act.
         # num_envs / tensorboard_log: accepted for signature compatibility with
         # ppo_deepset.py:53-75 (the env's num_envs is used; there is no tensorboard writer)
         self.env = env
@@ -162,6 +212,13 @@ class PPO_DeepSets:
         # rollout either way): the rollout is GPU-bound, so it runs eagerly.
         self._u = torch.zeros((T, B), device=dev)
         self.fused_act = bool(fused_act) and fused.sample_supported(self.agent, self.obs[0])
+        self.fused_bookkeeping = bool(fused_bookkeeping) and dev.type == "cuda" and hasattr(env, "record_ppo")
+        self.advantages = self.returns = None  # the last update()'s
+        if self.fused_bookkeeping:
+            self._ep_sum = torch.zeros(B, dtype=torch.float64, device=dev)  # per env (lb_ppo_record)
+            self._ep_cnt = torch.zeros(B, dtype=torch.float64, device=dev)
+            self._next_done = torch.zeros(B, device=dev)  # the done flags after the last step
+            self._gae_out = (torch.zeros((T, B), device=dev), torch.zeros((T, B), device=dev))
 
     def _rollout_body(self, next_done):
         """The T vector steps on the storage buffers (no host sync, no RNG call: the uniforms
@@ -169,8 +226,12 @@ class PPO_DeepSets:
         env = self.env
         T = self.num_steps
         next_obs = self.obs[0]
+        fb = self.fused_bookkeeping
+        if fb:  # record_ppo writes every later row
+            self.dones[0] = next_done
         for step in range(T):
-            self.dones[step] = next_done
+            if not fb:
+                self.dones[step] = next_done
             if self.fused_act:  # one launch: the sample and its storage rows (no masks, :169)
                 self.agent.act(next_obs, uniforms=self._u[step],
                                out=dict(actions_out=self._act, actions_f32_out=self.actions[step],
@@ -184,6 +245,10 @@ class PPO_DeepSets:
             # the env writes the next observation straight into the next storage slot
             next_obs = self.obs[step + 1] if step + 1 < T else self._last_obs
             env.step_device(self._act, obs_out=next_obs, reward_out=self.rewards[step], done_out=self._done_u8)
+            if fb:  # one launch: the next done row, the episode sums, the VecMonitor log
+                next_done = self.dones[step + 1] if step + 1 < T else self._next_done
+                env.record_ppo(self._done_u8, self.rewards[step], self._act, next_done, self._ep_sum, self._ep_cnt)
+                continue
             env.record_episodes(self._done_u8, self.rewards[step], self._act)  # VecMonitor file, if any
             next_done = self._done_u8.float()
             # finished-episode returns accumulate on the device (no per-step host sync)
@@ -294,8 +359,13 @@ class PPO_DeepSets:
     def update(self, next_obs, next_done):
         with torch.no_grad():
             next_value = self.agent.get_value(next_obs).reshape(1, -1)
-            advantages, returns = compute_gae(self.rewards, self.values, self.dones, next_value, next_done,
-                                              self.gamma, self.gae_lambda)
+            if self.fused_bookkeeping:  # one launch into the preallocated buffers
+                advantages, returns = gae_device(self.rewards, self.values, self.dones, next_value, next_done,
+                                                 self.gamma, self.gae_lambda, out=self._gae_out)
+            else:
+                advantages, returns = compute_gae(self.rewards, self.values, self.dones, next_value, next_done,
+                                                  self.gamma, self.gae_lambda)
+        self.advantages, self.returns = advantages, returns
         R = self.obs.shape[2]
         b_obs = self.obs.reshape(-1, R, 8)
         b_logprobs = self.logprobs.reshape(-1)

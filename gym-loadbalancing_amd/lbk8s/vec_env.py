@@ -400,6 +400,35 @@ class LBVecEnv:
         if len(self._log_times) >= self._log_every:
             self.flush_monitor()
 
+    def record_ppo(self, dones, rewards, actions, next_done_out, ep_sum, ep_cnt):
+        """PPO's bookkeeping of the last vector step in one launch (lb_ppo_record): the done
+        flags as float32 into next_done_out (B,) (the next row of the learner's `dones`
+        storage), the finished envs' returns added to the per-env float64 accumulators ep_sum /
+        ep_cnt (B,), and everything record_episodes does (the episode-log append, its step time
+        and the flush cadence) when the env is monitored; no log otherwise."""
+        t = self.torch
+        B = self.num_envs
+        for name, x, dt in (("dones", dones, t.uint8), ("rewards", rewards, t.float32), ("actions", actions, t.int32),
+                            ("next_done_out", next_done_out, t.float32), ("ep_sum", ep_sum, t.float64),
+                            ("ep_cnt", ep_cnt, t.float64)):
+            if (not isinstance(x, t.Tensor) or x.dtype != dt or tuple(x.shape) != (B,) or not x.is_contiguous()
+                    or x.device != self.ep_stats.device):
+                raise ValueError(f"record_ppo: {name} must be a contiguous ({B},) {dt} tensor on "
+                                 f"{self.ep_stats.device}")
+        head = (B, self._ptr(dones), self._ptr(self.ep_stats), self._ptr(next_done_out), self._ptr(ep_sum),
+                self._ptr(ep_cnt))
+        if not self.monitor:
+            _native.check(self._L.lb_ppo_record(*head, None, None, None, None, None, 0, None, 0, None,
+                                                self._stream()))
+            return
+        _native.check(self._L.lb_ppo_record(
+            *head, self._ptr(rewards), self._rew64, self._ptr(actions), self._ptr(self._ret32),
+            self._ptr(self._ep_r32), len(self._log_times), self._ptr(self._log), B, self._ptr(self._log_count),
+            self._stream()))
+        self._log_times.append(time.time())
+        if len(self._log_times) >= self._log_every:
+            self.flush_monitor()
+
     def flush_monitor(self):
         """Write the logged episodes (one host sync): in step order, env order within a step."""
         if not self.monitor or not self._log_times:

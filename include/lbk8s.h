@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LBK8S_ABI_VERSION 16
+#define LBK8S_ABI_VERSION 17
 
 /* reward_function names of loadbalancer_k8s_env.py:20-31 */
 enum { LB_REWARD_NAIVE = 0, LB_REWARD_LATENCY = 1, LB_REWARD_FAIRNESS = 2, LB_REWARD_MULTI = 3 };
@@ -399,6 +399,48 @@ enum { LB_EPLOG_RET32 = 16, LB_EPLOG_REWARD = 17, LB_EPLOG_ACTION = 18, LB_EPLOG
 int lb_episode_log(int64_t num_envs, const uint8_t* done, const double* ep_stats, const float* reward,
                    const double* reward64, const int32_t* actions, float* ret32, float* ep_r32, int64_t tag, double* log, int64_t cap,
                    uint32_t* count, void* stream);
+
+/* ---- PPO on the device (ABI 17): the rollout's per-step bookkeeping and GAE, one launch each.
+ * Both follow the conventions above: device pointers owned by the caller, asynchronous on
+ * `stream`, no allocation and no host synchronisation (capturable in a HIP graph), < 0 plus
+ * lb_last_error() on bad arguments, which are checked on the host before any device call.
+ *
+ * lb_ppo_record: one launch after a vector step (envs/ppo_deepset.py:174-190).  Per env b:
+ *   next_done_out[b] = done[b] ? 1.f : 0.f        (the next step's row of PPO's `dones` storage)
+ *   if done[b]: ep_sum[b] += ep_stats[b][LB_ST_RETURN], ep_cnt[b] += 1.0
+ * ep_sum / ep_cnt [B] f64 are per-env accumulators with no cross-env reduction, as
+ * lb_replay_add's: deterministic, summed by the caller once per rollout; both NULL or both given.
+ * With log != NULL the call also has exactly the effect of lb_episode_log(num_envs, done,
+ * ep_stats, reward, reward64, actions, ret32, ep_r32, tag, log, cap, count) (one definition of
+ * that kernel's body serves both): ret32, ep_r32, *count and the appended rows as that call
+ * writes them, rows unordered within a call, rows past cap dropped but counted.  log == NULL
+ * skips all of it: reward .. count are then not read or written.
+ * Refused: num_envs < 1; done, ep_stats or next_done_out NULL; one of ep_sum / ep_cnt alone; a
+ * log without reward, actions, ret32 or count, or with cap < 0. */
+int lb_ppo_record(int64_t num_envs, const uint8_t* done, const double* ep_stats,
+                  float* next_done_out, double* ep_sum, double* ep_cnt,
+                  const float* reward, const double* reward64, const int32_t* actions,
+                  float* ret32, float* ep_r32, int64_t tag, double* log, int64_t cap,
+                  uint32_t* count, void* stream);
+
+/* lb_gae: generalised advantage estimation (envs/ppo_deepset.py:192-205) over a rollout's
+ * storage in one launch, one thread per env.  rewards, values, dones, advantages_out,
+ * returns_out [T][B] f32; next_value, next_done [B] f32 (the bootstrap value and the done flags
+ * after the last step).  float32, op for op as the reference's tensor expression evaluates, no
+ * contraction; the constants are rounded once on the host, g = (float)gamma and
+ * gl = (float)(gamma * gae_lambda) (the product in double, as Python takes it).  With
+ *   nnt = 1 - (t == T-1 ? next_done[b] : dones[t+1][b]),  nv = t == T-1 ? next_value[b] : values[t+1][b]
+ * for t = T-1 .. 0, last = 0 before t = T-1:
+ *   delta = (rewards[t][b] + (g * nv) * nnt) - values[t][b]
+ *   last  = delta + (gl * nnt) * last
+ *   advantages_out[t][b] = last,  returns_out[t][b] = last + values[t][b]
+ * 64-bit indexing (T * B may pass 2^31); no LDS, no atomics.
+ * Refused: num_steps < 1; num_envs < 1; any NULL pointer; an output pointer equal to an input
+ * or to the other output. */
+int lb_gae(const float* rewards, const float* values, const float* dones,
+           const float* next_value, const float* next_done,
+           int64_t num_steps, int64_t num_envs, double gamma, double gae_lambda,
+           float* advantages_out, float* returns_out, void* stream);
 
 /* ---- Fused deep-sets training -----------------------------
  * Replaces the reference's autograd through the same modules in the PPO update

@@ -46,6 +46,9 @@ def parse():
     ap.add_argument("--fused-act", action="store_true",
                     help="PPO: the rollout's policy step as one launch (PPO_DeepSets(fused_act=True): lb_ds_sample "
                          "writes the action and the storage rows)")
+    ap.add_argument("--fused-bookkeeping", action="store_true",
+                    help="PPO: the rollout step's bookkeeping and GAE as one launch each "
+                         "(PPO_DeepSets(fused_bookkeeping=True): lb_ppo_record, lb_gae)")
     return ap.parse_args()
 
 
@@ -93,8 +96,9 @@ def main():
     if args.algo == "ppo":
         from lbk8s.ppo import PPO_DeepSets
         ppo = PPO_DeepSets(env, num_steps=args.num_steps, n_minibatches=8, update_epochs=4, ent_coef=0.001,
-                           gamma=0.95, gae_lambda=0.97, seed=1, device=dev, fused_act=args.fused_act)
-        out.update(fused_act=ppo.fused_act)
+                           gamma=0.95, gae_lambda=0.97, seed=1, device=dev, fused_act=args.fused_act,
+                           fused_bookkeeping=args.fused_bookkeeping)
+        out.update(fused_act=ppo.fused_act, fused_bookkeeping=ppo.fused_bookkeeping)
         next_obs = env.reset()
         next_done = torch.zeros(B, device=dev)
         for _ in range(args.warmup_updates):
