@@ -26,6 +26,7 @@
 #include "lbk8s_deepsets.h"
 #include "lbk8s_ds_train.h"
 #include "lbk8s_dqn.h"
+#include "lbk8s_ppo.h"
 #include "lbk8s_slice.h"
 #include "lbk8s_tpe.h"
 #include "lbk8s_rollout.h"
@@ -1245,6 +1246,58 @@ int lb_dqn_steps(const float* frag, float* obs, int64_t num_envs, int32_t num_el
     return dqn_steps_launch(frag, obs, num_envs, num_elements, masks, state, cfg, ex, actions_out, next_obs_out,
                             reward_out, done_out, terminal_obs_out, ep_stats_out, slots, pos_in, pos_out, rb_obs,
                             rb_next_obs, rb_actions, rb_rewards, rb_dones, ep_sum, ep_cnt, steps, sync, stream);
+}
+
+namespace {
+// lb_ppo_steps' shape: lb_dqn_step's one-launch shape (a property of the shape only), Philox draws
+// and a forward over exactly the env's actions
+bool ppo_steps_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    const int32_t A = cfg->num_endpoints + (cfg->rejection_allowed ? 1 : 0);
+    return num_envs >= 1 && cfg->rng_mode == LB_RNG_PHILOX && num_elements == A &&
+           dqn_step_fusable(cfg, num_envs, num_elements);
+}
+}  // namespace
+
+int lb_ppo_steps_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    if (validate(cfg)) return 0;
+    return ppo_steps_fusable(cfg, num_envs, num_elements) ? 1 : 0;
+}
+
+int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_config* cfg, int64_t num_envs,
+                 int32_t num_elements, int32_t steps, int32_t store_rows, const float* uniforms, float* actions_f32,
+                 float* logprobs, float* values, float* rewards, float* obs_next, float* dones_next, float* last_obs,
+                 float* last_done, int32_t* actions_out, uint8_t* done_out, double* ep_stats_out, double* ep_sum,
+                 double* ep_cnt, float* ret32, float* ep_r32, int64_t tag0, double* log, int64_t cap, uint32_t* count,
+                 void* stream) {
+    static_assert(2 * 16 <= DQN_OBS_F4, "the LDS observation image holds R <= 16 rows");
+    if (int r = validate(cfg)) return r;
+    if (num_envs < 1) return fail("lb_ppo_steps: num_envs < 1");
+    if (steps < 1 || steps > LB_PPO_STEPS_MAX) return fail("lb_ppo_steps: steps must be in [1, 4096]");
+    if (store_rows != steps && store_rows != steps - 1)
+        return fail("lb_ppo_steps: store_rows must be steps or steps - 1");
+    if (!frag || !obs || !state || !uniforms || !actions_f32 || !logprobs || !values || !rewards || !actions_out ||
+        !done_out || !ep_stats_out)
+        return fail("lb_ppo_steps: frag/obs/state/uniforms/actions_f32/logprobs/values/rewards/actions_out/done_out/"
+                    "ep_stats_out NULL");
+    if (store_rows > 0 && (!obs_next || !dones_next)) return fail("lb_ppo_steps: obs_next / dones_next NULL");
+    if (store_rows < steps && (!last_obs || !last_done))
+        return fail("lb_ppo_steps: store_rows == steps - 1 needs last_obs and last_done");
+    if ((ep_sum == nullptr) != (ep_cnt == nullptr)) return fail("lb_ppo_steps: ep_sum and ep_cnt go together");
+    if (log && (!ret32 || !count || cap < 0)) return fail("lb_ppo_steps: a log needs ret32, count and cap >= 0");
+    if (!ppo_steps_fusable(cfg, num_envs, num_elements))
+        return fail("lb_ppo_steps: the env's shape has no one-launch rollout (lb_ppo_steps_supported)");
+    Params e = make_params(state, cfg, num_envs);
+    e.done = done_out;
+    e.ep_stats = ep_stats_out;
+    DSParams d{nullptr, frag, nullptr, nullptr, num_envs, num_elements, 1, 1, nullptr, nullptr, nullptr, nullptr,
+               actions_out, nullptr};
+    PPOSteps r{steps, store_rows, obs, uniforms, actions_f32, logprobs, values, rewards,
+               reinterpret_cast<float4*>(obs_next), dones_next, reinterpret_cast<float4*>(last_obs), last_done,
+               ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count};
+    constexpr int P = 2;  // envs per wave iteration (the LDS budget: lbk8s_ppo.h)
+    const unsigned grid = ds_grid_spread((num_envs + P - 1) / P);
+    hipLaunchKernelGGL(k_ppo_steps<P>, dim3(grid), dim3(DS_BLOCK), 0, (hipStream_t)stream, d, e, r);
+    return check_launch();
 }
 
 int lb_dqn_head(const float* q, const float* q_next, const int64_t* actions, const float* rewards, const float* dones,

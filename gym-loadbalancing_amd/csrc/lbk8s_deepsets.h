@@ -332,9 +332,10 @@ __device__ __forceinline__ int64_t ds_uniform(int64_t v) {
 // lg[s * TS + t]: env env0 + s's masked logit of row 16 t + col (every row group holds a copy),
 // -inf past R.  The scan of a tile is row_scan plus the earlier tiles' total; the lane of row
 // group 0 that holds the action's row writes the set's outputs.
+// Returns env0 + s's action on the lanes of row group s (s < P; lb_ppo_steps steps the env there).
 template <int TS, int P>
-__device__ __forceinline__ void ds_sample_group(const DSParams& p, const float (&lg)[P * TS], int64_t env0, int col,
-                                                int grp) {
+__device__ __forceinline__ int32_t ds_sample_group(const DSParams& p, const float (&lg)[P * TS], int64_t env0, int col,
+                                                   int grp) {
     env0 = ds_uniform(env0);
     float m[P];
 #pragma unroll
@@ -368,9 +369,11 @@ __device__ __forceinline__ void ds_sample_group(const DSParams& p, const float (
         fl[2 * s + 1] = last;
     }
     row_reduce<true>(fl);
+    int32_t mine = -1;
 #pragma unroll
     for (int s = 0; s < P; ++s) {
         const int a = fl[2 * s] > -1e8f ? (int)(-fl[2 * s]) : (int)fl[2 * s + 1];
+        mine = grp == s ? a : mine;
         if (grp != 0 || col != (a & 15) || env0 + s >= p.B) continue;
         float la = lg[s * TS];
 #pragma unroll
@@ -379,6 +382,7 @@ __device__ __forceinline__ void ds_sample_group(const DSParams& p, const float (
         if (p.actions_f32) p.actions_f32[env0 + s] = (float)a;
         p.logprob[env0 + s] = (la - m[s]) - logf(S[s]);
     }
+    return mine;
 }
 
 // A wave iteration holds P envs of TS set tiles each: fragment array h[P*TS][KS], tile
@@ -624,7 +628,8 @@ __device__ __forceinline__ void ds_group_obs(const DSParams& p, int64_t env0, in
 }
 
 // one wave iteration's P envs: the actor (or Q network) Eq(8->64) ReLU Eq(64->64) ELU Eq(64->1);
-// logits / training rows / the masked greedy action (ARGMAX: lane s < P returns env0 + s's)
+// logits / training rows / the masked greedy action (ARGMAX: lane s < P returns env0 + s's) / the
+// sampled action (SAMPLE: the lanes of row group s < P return env0 + s's)
 // (W: the fragment image, or the VALU image with xs the wave's scratch: DSGeom<TS, P>::VG)
 template <int TS, int P, int MODE, bool VG = DSGeom<TS, P, MODE>::VG, bool XR = false>
 __device__ __forceinline__ int32_t ds_group_actor(const DSParams& p, const float* W, int lane, int64_t env0, int col,
@@ -727,9 +732,163 @@ __device__ __forceinline__ int32_t ds_group_actor(const DSParams& p, const float
                 act = (int32_t)r;
             }
         }
-        if constexpr (SAMPLE) ds_sample_group<TS, P>(p, lg, env0, col, grp);
+        if constexpr (SAMPLE) act = ds_sample_group<TS, P>(p, lg, env0, col, grp);
     }
     return act;
+}
+
+// one wave iteration's P envs: the critic (psi = Eq ELU Eq ELU Eq, mean over the set, rho) from
+// ds_group_obs's fragments; the value / the training forward's psi mean (W, xs: as ds_group_actor)
+template <int TS, int P, int MODE, bool VG = DSGeom<TS, P, MODE>::VG, bool XR = false>
+__device__ __forceinline__ void ds_group_critic(const DSParams& p, const float* W, int lane, int64_t env0, int col,
+                                                int grp, int R, const float (&h0)[P * TS][2], const float (&m0)[2],
+                                                float* xs = nullptr, const float* xr0 = nullptr) {
+    constexpr bool TRAIN = MODE == 1;
+    float h1[P * TS][16], m1[16], h2[P * TS][16], m2[16];
+
+    // ---- critic: psi = Eq ELU Eq ELU Eq, mean over the set, rho = Linear ELU Linear
+    constexpr int C1L = VG ? VG_C1L : DS_C1L, C1G = VG ? VG_C1G : DS_C1G, C2L = VG ? VG_C2L : DS_C2L,
+                  C2G = VG ? VG_C2G : DS_C2G;
+    float g = 0.f, c1r = 0.f, xr[16];  // (XR: the extra row, as the actor's)
+    eq_layer<TS, P, 2, 2, VG>(W + C1L, W + C1G, h0, m0, h1, lane, xs, XR ? &g : nullptr);
+    if constexpr (XR) {
+        c1r = vg_xrow<2, 2>(W + VGX_C1, xr0, 0.f, g, xs, lane);
+        vg_xspread(c1r, xs, lane, xr);
+        store_xrow(p.save_critic, c1r, env0, p.B, R, lane);
+    }
+    if (TRAIN) store_rows<TS, P>(p.save_critic, h1, env0, p.B, R, col, grp);
+    if (TRAIN)
+        set_max_store<TS, P, 16>(h1, m1, col, grp, R, env0, p.B, p.setvec, LB_DSV_MAX1C, LB_DSV_ID1C,
+                                 XR ? xr : nullptr);
+    else set_max_batched<TS, P, 16>(h1, m1, col, R);
+    eq_layer<TS, P, 16, 2, VG>(W + C2L, W + C2G, h1, m1, h2, lane, xs, XR ? &g : nullptr);
+    if constexpr (XR) {
+        const float c2r = vg_xrow<16, 2>(W + VGX_C2, nullptr, c1r, g, xs, lane);
+        vg_xspread(c2r, xs, lane, xr);  // (xr: c2's extra row, into the max and the sum)
+        store_xrow(p.save_critic + p.B * (int64_t)R * 64, c2r, env0, p.B, R, lane);
+    }
+    if (TRAIN) store_rows<TS, P>(p.save_critic + p.B * (int64_t)R * 64, h2, env0, p.B, R, col, grp);
+    if (TRAIN)
+        set_max_store<TS, P, 16>(h2, m2, col, grp, R, env0, p.B, p.setvec, LB_DSV_MAX2C, LB_DSV_ID2C,
+                                 XR ? xr : nullptr);
+    else set_max_batched<TS, P, 16>(h2, m2, col, R);
+    // layer 3 has no activation and only its mean over the set is used, so
+    // mean_r(Lambda3 c2[r] - Gamma3 max(c2)) = Lambda3 mean_r(c2) - Gamma3 max(c2): one
+    // matrix-vector pair on the batched (column c = env c mod P) operands instead of a
+    // 64x64 layer over every row
+    if constexpr (VG) {  // the pair, rho's two layers: lane f's dot products (xs: x, then y)
+        float sm[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            float v = 0.f;
+#pragma unroll
+            for (int t = 0; t < TS; ++t)
+                if (16 * t + col < R) v += h2[t][k];
+            sm[k] = v;
+        }
+        row_reduce<false>(sm);
+        if constexpr (XR) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) sm[k] += xr[k];
+        }
+        const float invR = 1.0f / (float)R;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) sm[k] *= invR;
+        vg_put<16>(m2, xs, col, grp);
+        ds_wave_fence();
+        float mean = vg_dot<64, VG_RS>(W + VG_C3G, xs, lane, 0.f);  // (-Gamma3) max, then Lambda3 mean
+        ds_wave_fence();
+        vg_put<16>(sm, xs, col, grp);
+        ds_wave_fence();
+        mean = vg_dot<64, VG_RS>(W + VG_C3L, xs, lane, mean);
+        if (TRAIN) {
+            if (env0 < p.B) p.psi_mean[env0 * 64 + lane] = mean;
+            ds_wave_fence();
+            return;
+        }
+        ds_wave_fence();
+        xs[lane] = mean;
+        ds_wave_fence();
+        const float r1 = act_elu(vg_dot<64, VG_RS>(W + VG_R1W, xs, lane, W[VG_R1B + lane]));
+        float v[1] = {W[VG_R2W + lane] * r1};
+        row_reduce<false>(v);
+        v[0] += __shfl_xor(v[0], 16);
+        v[0] += __shfl_xor(v[0], 32);
+        if (lane == 0 && env0 < p.B) p.value[env0] = W[VG_R2B] + v[0];
+        ds_wave_fence();
+        return;
+    }
+    float mean[16];
+    {
+        const float invR = 1.0f / (float)R;
+        float sm[16 * P], mc[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+#pragma unroll
+            for (int s = 0; s < P; ++s) {
+                float v = 0.f;
+#pragma unroll
+                for (int t = 0; t < TS; ++t)
+                    if (16 * t + col < R) v += h2[s * TS + t][k];
+                sm[k * P + s] = v;
+            }
+        row_reduce<false>(sm);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            float r = sm[k * P];
+#pragma unroll
+            for (int s = 1; s < P; ++s) r = (col % P == s) ? sm[k * P + s] : r;
+            mc[k] = r * invR;
+        }
+        // (the four output tiles' chains side by side; each element: Gamma then Lambda, k in order)
+        dsf4 acc[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[nt] = dsf4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma4(W[DS_C3G + (nt * 16 + k) * 64 + lane], m2[k], acc[nt]);
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma4(W[DS_C3L + (nt * 16 + k) * 64 + lane], mc[k], acc[nt]);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mean[4 * nt + i] = acc[nt][i];
+    }
+    if (TRAIN) {
+        // column c carries env (c mod P): lanes of columns < P store their env's features
+        if (col < P && env0 + col < p.B) {
+            float* q = p.psi_mean + (env0 + col) * 64 + 4 * grp;
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+                *reinterpret_cast<float4*>(q + 16 * nt) =
+                    make_float4(mean[4 * nt], mean[4 * nt + 1], mean[4 * nt + 2], mean[4 * nt + 3]);
+        }
+        return;
+    }
+    float r1[16];
+    {
+        dsf4 acc[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[nt][i] = W[DS_R1B + 16 * nt + 4 * grp + i];
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma4(W[DS_R1W + (nt * 16 + k) * 64 + lane], mean[k], acc[nt]);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r1[4 * nt + i] = act_elu(acc[nt][i]);
+    }
+    dsf4 v = {W[DS_R2B], 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v = mfma4(W[DS_R2W + k * 64 + lane], r1[k], v);
+    // row 0 of the result: column c = env (c mod P)
+    if (grp == 0 && col < P && env0 + col < p.B) p.value[env0 + col] = v[0];
 }
 
 // MODE 0: logits / value; 1: training forward (TRAIN: activations, psi mean); 2: Q values
@@ -739,7 +898,7 @@ __device__ __forceinline__ int32_t ds_group_actor(const DSParams& p, const float
 // its half of the grid), W the block's LDS weight region
 template <int TS, int P, int MODE, bool XR = false>
 __device__ __forceinline__ void ds_fwd_body(const DSParams& p, float* W, int blk, int nblk) {
-    constexpr bool TRAIN = MODE == 1, ARGMAX = MODE == 2, VG = DSGeom<TS, P, MODE, XR>::VG;
+    constexpr bool ARGMAX = MODE == 2, VG = DSGeom<TS, P, MODE, XR>::VG;
     // stage the weight image (once per block; blocks are persistent): the fragment image, or
     // the VALU image (VG: the actor's and critic's regions, rho's for the inference forward, the
     // extra-row block for XR); an actor-only launch (DQN) stages only the actor's part
@@ -769,152 +928,8 @@ __device__ __forceinline__ void ds_fwd_body(const DSParams& p, float* W, int blk
         float h0[P * TS][2], m0[2], xr0[2];
         ds_group_obs<TS, P, MODE, XR>(p, env0, col, grp, R, h0, m0, xr0);
         ds_group_actor<TS, P, MODE, VG, XR>(p, W, lane, env0, col, grp, R, h0, m0, xs, xr0);
-        float h1[P * TS][16], m1[16], h2[P * TS][16], m2[16];
         if (ARGMAX || !p.critic) continue;
-
-        // ---- critic: psi = Eq ELU Eq ELU Eq, mean over the set, rho = Linear ELU Linear
-        constexpr int C1L = VG ? VG_C1L : DS_C1L, C1G = VG ? VG_C1G : DS_C1G, C2L = VG ? VG_C2L : DS_C2L,
-                      C2G = VG ? VG_C2G : DS_C2G;
-        float g = 0.f, c1r = 0.f, xr[16];  // (XR: the extra row, as the actor's)
-        eq_layer<TS, P, 2, 2, VG>(W + C1L, W + C1G, h0, m0, h1, lane, xs, XR ? &g : nullptr);
-        if constexpr (XR) {
-            c1r = vg_xrow<2, 2>(W + VGX_C1, xr0, 0.f, g, xs, lane);
-            vg_xspread(c1r, xs, lane, xr);
-            store_xrow(p.save_critic, c1r, env0, p.B, R, lane);
-        }
-        if (TRAIN) store_rows<TS, P>(p.save_critic, h1, env0, p.B, R, col, grp);
-        if (TRAIN)
-            set_max_store<TS, P, 16>(h1, m1, col, grp, R, env0, p.B, p.setvec, LB_DSV_MAX1C, LB_DSV_ID1C,
-                                     XR ? xr : nullptr);
-        else set_max_batched<TS, P, 16>(h1, m1, col, R);
-        eq_layer<TS, P, 16, 2, VG>(W + C2L, W + C2G, h1, m1, h2, lane, xs, XR ? &g : nullptr);
-        if constexpr (XR) {
-            const float c2r = vg_xrow<16, 2>(W + VGX_C2, nullptr, c1r, g, xs, lane);
-            vg_xspread(c2r, xs, lane, xr);  // (xr: c2's extra row, into the max and the sum)
-            store_xrow(p.save_critic + p.B * (int64_t)R * 64, c2r, env0, p.B, R, lane);
-        }
-        if (TRAIN) store_rows<TS, P>(p.save_critic + p.B * (int64_t)R * 64, h2, env0, p.B, R, col, grp);
-        if (TRAIN)
-            set_max_store<TS, P, 16>(h2, m2, col, grp, R, env0, p.B, p.setvec, LB_DSV_MAX2C, LB_DSV_ID2C,
-                                     XR ? xr : nullptr);
-        else set_max_batched<TS, P, 16>(h2, m2, col, R);
-        // layer 3 has no activation and only its mean over the set is used, so
-        // mean_r(Lambda3 c2[r] - Gamma3 max(c2)) = Lambda3 mean_r(c2) - Gamma3 max(c2): one
-        // matrix-vector pair on the batched (column c = env c mod P) operands instead of a
-        // 64x64 layer over every row
-        if constexpr (VG) {  // the pair, rho's two layers: lane f's dot products (xs: x, then y)
-            float sm[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                float v = 0.f;
-#pragma unroll
-                for (int t = 0; t < TS; ++t)
-                    if (16 * t + col < R) v += h2[t][k];
-                sm[k] = v;
-            }
-            row_reduce<false>(sm);
-            if constexpr (XR) {
-#pragma unroll
-                for (int k = 0; k < 16; ++k) sm[k] += xr[k];
-            }
-            const float invR = 1.0f / (float)R;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) sm[k] *= invR;
-            vg_put<16>(m2, xs, col, grp);
-            ds_wave_fence();
-            float mean = vg_dot<64, VG_RS>(W + VG_C3G, xs, lane, 0.f);  // (-Gamma3) max, then Lambda3 mean
-            ds_wave_fence();
-            vg_put<16>(sm, xs, col, grp);
-            ds_wave_fence();
-            mean = vg_dot<64, VG_RS>(W + VG_C3L, xs, lane, mean);
-            if (TRAIN) {
-                if (env0 < p.B) p.psi_mean[env0 * 64 + lane] = mean;
-                ds_wave_fence();
-                continue;
-            }
-            ds_wave_fence();
-            xs[lane] = mean;
-            ds_wave_fence();
-            const float r1 = act_elu(vg_dot<64, VG_RS>(W + VG_R1W, xs, lane, W[VG_R1B + lane]));
-            float v[1] = {W[VG_R2W + lane] * r1};
-            row_reduce<false>(v);
-            v[0] += __shfl_xor(v[0], 16);
-            v[0] += __shfl_xor(v[0], 32);
-            if (lane == 0 && env0 < p.B) p.value[env0] = W[VG_R2B] + v[0];
-            ds_wave_fence();
-            continue;
-        }
-        float mean[16];
-        {
-            const float invR = 1.0f / (float)R;
-            float sm[16 * P], mc[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-#pragma unroll
-                for (int s = 0; s < P; ++s) {
-                    float v = 0.f;
-#pragma unroll
-                    for (int t = 0; t < TS; ++t)
-                        if (16 * t + col < R) v += h2[s * TS + t][k];
-                    sm[k * P + s] = v;
-                }
-            row_reduce<false>(sm);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                float r = sm[k * P];
-#pragma unroll
-                for (int s = 1; s < P; ++s) r = (col % P == s) ? sm[k * P + s] : r;
-                mc[k] = r * invR;
-            }
-            // (the four output tiles' chains side by side; each element: Gamma then Lambda, k in order)
-            dsf4 acc[4];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[nt] = dsf4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma4(W[DS_C3G + (nt * 16 + k) * 64 + lane], m2[k], acc[nt]);
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma4(W[DS_C3L + (nt * 16 + k) * 64 + lane], mc[k], acc[nt]);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) mean[4 * nt + i] = acc[nt][i];
-        }
-        if (TRAIN) {
-            // column c carries env (c mod P): lanes of columns < P store their env's features
-            if (col < P && env0 + col < p.B) {
-                float* q = p.psi_mean + (env0 + col) * 64 + 4 * grp;
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt)
-                    *reinterpret_cast<float4*>(q + 16 * nt) =
-                        make_float4(mean[4 * nt], mean[4 * nt + 1], mean[4 * nt + 2], mean[4 * nt + 3]);
-            }
-            continue;
-        }
-        float r1[16];
-        {
-            dsf4 acc[4];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[nt][i] = W[DS_R1B + 16 * nt + 4 * grp + i];
-#pragma unroll
-            for (int k = 0; k < 16; ++k)
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) acc[nt] = mfma4(W[DS_R1W + (nt * 16 + k) * 64 + lane], mean[k], acc[nt]);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) r1[4 * nt + i] = act_elu(acc[nt][i]);
-        }
-        dsf4 v = {W[DS_R2B], 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) v = mfma4(W[DS_R2W + k * 64 + lane], r1[k], v);
-        // row 0 of the result: column c = env (c mod P)
-        if (grp == 0 && col < P && env0 + col < p.B) p.value[env0 + col] = v[0];
+        ds_group_critic<TS, P, MODE, VG, XR>(p, W, lane, env0, col, grp, R, h0, m0, xs, xr0);
     }
 }
 

@@ -65,6 +65,13 @@ def build_parser():
     p.add_argument("--nproc", default=1, type=int, help="GPUs (ranks) to train on, one process each")
     p.add_argument("--monitor_file", default="vec_loadbalancer_k8s_gym_results",
                    help="VecMonitor file of the training envs (run.py:122); '' disables it")
+    p.add_argument("--fused-act", action="store_true",
+                   help="ppo_deepsets: the rollout's policy step as one launch (PPO_DeepSets(fused_act=True))")
+    p.add_argument("--fused-bookkeeping", action="store_true",
+                   help="ppo_deepsets: the rollout step's bookkeeping and GAE as one launch each")
+    p.add_argument("--fused-rollout", action="store_true",
+                   help="ppo_deepsets: a rollout's vector steps as one launch where the env's shape has it "
+                        "(E <= 16, R <= 16, fewer than 32,768 envs)")
     return p
 
 
@@ -86,14 +93,15 @@ def get_env(env_name, rejection, num_endpoints, num_zones, num_nodes, reward_fun
                     **env_kwargs(rejection, num_endpoints, num_zones, num_nodes, reward_function))
 
 
-def get_model(alg, env, rank=0):
+def get_model(alg, env, rank=0, **ppo_flags):
     """get_model (run.py:54-72) for the deep-sets algorithms.  With several ranks each rank's
     learner seed is offset by its rank, so rollout uniforms, minibatch permutations, replay
     samples and exploration coins differ across GPUs (the parameters are broadcast from rank
-    0, so the replicas still start identical)."""
+    0, so the replicas still start identical).  ppo_flags: PPO_DeepSets' fused_act /
+    fused_bookkeeping / fused_rollout (all off by default)."""
     if alg == "ppo_deepsets":
         from .ppo import PPO_DeepSets
-        return PPO_DeepSets(env, num_steps=100, n_minibatches=8, ent_coef=0.001, seed=2 + rank)
+        return PPO_DeepSets(env, num_steps=100, n_minibatches=8, ent_coef=0.001, seed=2 + rank, **ppo_flags)
     if alg == "dqn_deepsets":
         from .dqn import DQN_DeepSets
         return DQN_DeepSets(env, num_steps=100, n_minibatches=8, seed=1 + rank)
@@ -131,7 +139,9 @@ def main(argv=None):
         env = get_env(args.env_name, args.rejection, num_endpoints, num_zones, num_nodes, reward,
                       num_envs=args.num_envs, device=dev if world > 1 else args.device, seed=args.seed,
                       env_id_offset=rank * args.num_envs, monitor_file=mon)
-        model = get_model(alg, env, rank)
+        flags = dict(fused_act=args.fused_act, fused_bookkeeping=args.fused_bookkeeping,
+                     fused_rollout=args.fused_rollout) if alg == "ppo_deepsets" else {}
+        model = get_model(alg, env, rank, **flags)
         if args.loading:  # resume training
             model.load(args.load_path)
         model.learn(total_timesteps=total_steps)

@@ -22,7 +22,9 @@ capture's warm-up steps are undone (parameters restored, Adam state zeroed), so 
 path computes the same update as the eager one.
 
 With fused_act and fused_bookkeeping a rollout's vector step is three launches (lb_ds_sample,
-lb_step, lb_ppo_record) and GAE is one (lb_gae, gae_device); both flags are off by default.
+lb_step, lb_ppo_record) and GAE is one (lb_gae, gae_device); with fused_rollout the whole
+rollout's vector steps are ONE launch (lb_ppo_steps, LBVecEnv.ppo_steps) where the env's shape has
+it (E <= 16 below 32,768 envs, R <= 16).  All three flags are off by default.
 """
 import os
 import time
@@ -145,7 +147,7 @@ class PPO_DeepSets:
                  clip_vloss: bool = True, ent_coef: float = 0.01, vf_coef: float = 0.5,
                  max_grad_norm: float = 0.5, target_kl: Optional[float] = None, seed: int = 1,
                  device=None, log_fn=None, num_envs=None, tensorboard_log=None, use_graphs=None,
-                 fused_act: bool = False, fused_bookkeeping: bool = False):
+                 fused_act: bool = False, fused_bookkeeping: bool = False, fused_rollout: bool = False):
         # fused_act: the rollout's policy step as ONE launch (fused.deepsets_sample) that writes the
         # env's action buffer and the step's storage rows (actions, logprobs, values) directly.  Off
         # by default: a draw on a CDF boundary can pick the neighbouring row (and u = 0 never picks
@@ -155,6 +157,12 @@ class PPO_DeepSets:
         # launch (gae_device) instead of eager torch arithmetic.  Same storage, advantages and
         # monitor file, bit for bit; the logged mean return sums per-env float64 accumulators, so
         # it can differ from the default's in the last bits.  Off by default, as fused_act.
+        # fused_rollout: the T vector steps of a rollout as ONE launch (LBVecEnv.ppo_steps): each
+        # wave takes its envs through every step, the observations in LDS and the env in registers.
+        # The same storage, advantages and monitor file as fused_act + fused_bookkeeping, bit for
+        # bit, whose buffers it implies.  Effective where the sampling forward covers the agent,
+        # the env has the one-launch shape (ppo_steps_supported) and the device is HIP; elsewhere
+        # the attribute reads False and the other two flags decide.  Off by default.
         # num_envs / tensorboard_log: accepted for signature compatibility with
         # ppo_deepset.py:53-75 (the env's num_envs is used; there is no tensorboard writer)
         self.env = env
@@ -213,6 +221,10 @@ class PPO_DeepSets:
         self._u = torch.zeros((T, B), device=dev)
         self.fused_act = bool(fused_act) and fused.sample_supported(self.agent, self.obs[0])
         self.fused_bookkeeping = bool(fused_bookkeeping) and dev.type == "cuda" and hasattr(env, "record_ppo")
+        self.fused_rollout = (bool(fused_rollout) and dev.type == "cuda" and hasattr(env, "ppo_steps")
+                              and fused.sample_supported(self.agent, self.obs[0]) and env.ppo_steps_supported(R))
+        if self.fused_rollout:  # (its buffers are fused_bookkeeping's; GAE in one launch too)
+            self.fused_bookkeeping = True
         self.advantages = self.returns = None  # the last update()'s
         if self.fused_bookkeeping:
             self._ep_sum = torch.zeros(B, dtype=torch.float64, device=dev)  # per env (lb_ppo_record)
@@ -225,6 +237,13 @@ class PPO_DeepSets:
         are drawn before).  Returns the done flags after the last step."""
         env = self.env
         T = self.num_steps
+        if self.fused_rollout:  # one launch (per monitor flush): every storage row, the sums, the log
+            self.dones[0] = next_done
+            agent = self.agent
+            env.ppo_steps(fused.packed(agent, agent.actor.net, agent.critic), self.obs[0], self._u, self.actions,
+                          self.logprobs, self.values, self.rewards, self.obs[1:], self.dones[1:], self._last_obs,
+                          self._next_done, self._act, self._done_u8, self._ep_sum, self._ep_cnt)
+            return self._next_done
         next_obs = self.obs[0]
         fb = self.fused_bookkeeping
         if fb:  # record_ppo writes every later row

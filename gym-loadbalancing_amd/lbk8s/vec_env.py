@@ -429,6 +429,73 @@ class LBVecEnv:
         if len(self._log_times) >= self._log_every:
             self.flush_monitor()
 
+    def ppo_steps_supported(self, R):
+        """Whether lb_ppo_steps (a PPO rollout's vector steps in one launch) covers this env with
+        R-row observations."""
+        return bool(self._L.lb_ppo_steps_supported(C.byref(self._c), self.num_envs, R))
+
+    def ppo_steps(self, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next, dones_next,
+                  last_obs, last_done, actions, dones, ep_sum, ep_cnt):
+        """lb_ppo_steps: T = uniforms.shape[0] PPO vector steps -- each fused.deepsets_sample on the
+        weight image `frag` (no masks), step_device and record_ppo -- in one launch, bit for bit
+        those 3 T launches.  obs (B, R, 8) is the first step's input; uniforms, actions_f32,
+        logprobs, values and rewards are (T, B) float32; step i's next observation / done row go to
+        obs_next[i] / dones_next[i] (S, B, R, 8) / (S, B) for i < S, S = T or T - 1, else to
+        last_obs (B, R, 8) / last_done (B,) (required when S = T - 1, else None).  actions (B,)
+        int32 and dones (B,) uint8 end as the last step leaves them; ep_sum / ep_cnt (B,) float64
+        as record_ppo's.  A monitored env logs every step with its own host time and flushes at
+        record_ppo's cadence: the request is split into launches that end where a flush is due
+        (within that many steps an env finishes at most once, so the log cannot overflow)."""
+        t = self.torch
+        if not self._reset_called and not t.cuda.is_current_stream_capturing():
+            raise TypeError("step() called before reset()")
+        B, dev = self.num_envs, self.ep_stats.device
+        if not isinstance(uniforms, t.Tensor) or uniforms.dim() != 2 or uniforms.shape[0] < 1:
+            raise ValueError("ppo_steps: uniforms must be a (T, B) tensor with T >= 1")
+        if not isinstance(obs, t.Tensor) or obs.dim() != 3:
+            raise ValueError("ppo_steps: obs must be a (B, R, 8) tensor")
+        T, R = uniforms.shape[0], obs.shape[1]
+        S = obs_next.shape[0] if isinstance(obs_next, t.Tensor) and obs_next.dim() == 4 else -1
+        if S not in (T, T - 1):
+            raise ValueError(f"ppo_steps: obs_next must be a ({T} or {T - 1}, {B}, {R}, 8) tensor")
+        spec = [("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32), ("obs", obs, (B, R, 8), t.float32),
+                ("uniforms", uniforms, (T, B), t.float32), ("actions_f32", actions_f32, (T, B), t.float32),
+                ("logprobs", logprobs, (T, B), t.float32), ("values", values, (T, B), t.float32),
+                ("rewards", rewards, (T, B), t.float32), ("obs_next", obs_next, (S, B, R, 8), t.float32),
+                ("dones_next", dones_next, (S, B), t.float32), ("actions", actions, (B,), t.int32),
+                ("dones", dones, (B,), t.uint8), ("ep_sum", ep_sum, (B,), t.float64),
+                ("ep_cnt", ep_cnt, (B,), t.float64)]
+        if S < T or last_obs is not None or last_done is not None:
+            spec += [("last_obs", last_obs, (B, R, 8), t.float32), ("last_done", last_done, (B,), t.float32)]
+        for name, x, shape, dt in spec:
+            if (not isinstance(x, t.Tensor) or x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous()
+                    or x.device != dev):
+                raise ValueError(f"ppo_steps: {name} must be a contiguous {shape} {dt} tensor on {dev}")
+        if not self.ppo_steps_supported(R):
+            raise RuntimeError("ppo_steps: the env's shape has no one-launch rollout (ppo_steps_supported)")
+        i = 0
+        while i < T:
+            # a launch of steps i .. i + n - 1: the whole request, or up to the next flush
+            n = min(T - i, _native.LB_PPO_STEPS_MAX)
+            if self.monitor:
+                n = min(n, self._log_every - len(self._log_times))
+            s = min(n, S - i)  # rows of obs_next / dones_next this launch fills (n, or n - 1 at the end)
+            src = obs if i == 0 else obs_next[i - 1]
+            log = ((self._ptr(self._ret32), self._ptr(self._ep_r32), len(self._log_times), self._ptr(self._log), B,
+                    self._ptr(self._log_count)) if self.monitor else (None, None, 0, None, 0, None))
+            _native.check(self._L.lb_ppo_steps(
+                self._ptr(frag), self._ptr(src), self._ptr(self.state), C.byref(self._c), B, R, n, s,
+                self._ptr(uniforms[i]), self._ptr(actions_f32[i]), self._ptr(logprobs[i]), self._ptr(values[i]),
+                self._ptr(rewards[i]), self._ptr(obs_next[i]) if s else None,
+                self._ptr(dones_next[i]) if s else None, self._ptr(last_obs) if s < n else None,
+                self._ptr(last_done) if s < n else None, self._ptr(actions), self._ptr(dones),
+                self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt), *log, self._stream()))
+            i += n
+            if self.monitor:
+                self._log_times.extend(time.time() for _ in range(n))
+                if len(self._log_times) >= self._log_every:
+                    self.flush_monitor()
+
     def flush_monitor(self):
         """Write the logged episodes (one host sync): in step order, env order within a step."""
         if not self.monitor or not self._log_times:

@@ -442,6 +442,47 @@ int lb_gae(const float* rewards, const float* values, const float* dones,
            int64_t num_steps, int64_t num_envs, double gamma, double gae_lambda,
            float* advantages_out, float* returns_out, void* stream);
 
+/* ---- ABI 17, additions: a PPO rollout's vector steps in ONE launch (as lb_dqn_steps is for DQN).
+ * Over a rollout the policy is fixed, the uniforms are drawn beforehand and every output is per
+ * env, so each wave takes its envs through all `steps` (1..LB_PPO_STEPS_MAX) vector steps: the
+ * env in registers, the observations in LDS.  The call has exactly the effect, bit for bit, of
+ * running for i = 0 .. steps-1, with the same frag, state, cfg and stream:
+ *   lb_ds_sample(frag, obs_i, num_envs, num_elements, masks = NULL, uniforms + i B, logits = NULL,
+ *                actions_out, actions_f32 + i B, logprobs + i B, values + i B)
+ *   lb_step(state, cfg, num_envs, actions_out, obs_{i+1}, rewards + i B, done_out,
+ *           terminal_obs = NULL, ep_stats_out, trace = NULL)
+ *   lb_ppo_record(num_envs, done_out, ep_stats_out, done_{i+1}, ep_sum, ep_cnt, rewards + i B,
+ *                 the state's lb_reward64 array, actions_out, ret32, ep_r32, tag0 + i, log, cap, count)
+ * where B = num_envs, obs_0 = obs, and obs_{i+1} / done_{i+1} are row i of obs_next
+ * [store_rows][B][R][8] / dones_next [store_rows][B] for i < store_rows, else last_obs [B][R][8] /
+ * last_done [B].  store_rows is steps or steps - 1 (PPO's storage: obs_next = obs[1:], the state
+ * after the last step kept apart); with store_rows == steps, last_obs / last_done are not used
+ * and may be NULL, with store_rows == 0, obs_next / dones_next.  uniforms, actions_f32, logprobs,
+ * values, rewards are [steps][B] f32.  actions_out, done_out, ep_stats_out and the lb_reward64
+ * array end as the last lb_step leaves them (an ep_stats row is written when its env's episode
+ * ends, at any step).  ep_sum / ep_cnt, ret32 / ep_r32 / log / cap / count: as lb_ppo_record
+ * (log == NULL: no episode log; rows unordered within the call; rows past cap dropped but counted).
+ * No host synchronisation, no allocation, capturable in a HIP graph; arguments are checked on the
+ * host before any device call.
+ * Supported (lb_ppo_steps_supported == 1; a property of the shape, never of the device):
+ * lb_dqn_steps' shape (the slice layout with 16 lanes per env: E <= 16 below 32,768 envs;
+ * num_elements <= 16) in Philox mode with num_elements the env's action count.
+ * Refused: num_envs < 1; steps outside [1, LB_PPO_STEPS_MAX]; store_rows not steps or steps - 1;
+ * a NULL among frag, obs, state, uniforms, actions_f32, logprobs, values, rewards, actions_out,
+ * done_out, ep_stats_out; obs_next / dones_next NULL with store_rows > 0; last_obs / last_done NULL
+ * with store_rows == steps - 1; one of ep_sum / ep_cnt alone; a log without ret32 or count, or with
+ * cap < 0; an unsupported shape (there is no fallback: ask lb_ppo_steps_supported first). */
+#define LB_PPO_STEPS_MAX 4096
+int lb_ppo_steps_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements);
+int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_config* cfg,
+                 int64_t num_envs, int32_t num_elements, int32_t steps, int32_t store_rows,
+                 const float* uniforms, float* actions_f32, float* logprobs, float* values, float* rewards,
+                 float* obs_next, float* dones_next, float* last_obs, float* last_done,
+                 int32_t* actions_out, uint8_t* done_out, double* ep_stats_out,
+                 double* ep_sum, double* ep_cnt,
+                 float* ret32, float* ep_r32, int64_t tag0, double* log, int64_t cap, uint32_t* count,
+                 void* stream);
+
 /* ---- Fused deep-sets training -----------------------------
  * Replaces the reference's autograd through the same modules in the PPO update
  * (envs/ppo_deepset.py:227-263 -> deep_sets_agent_original.py:56-106).  The training

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """tests/test_gpu_learners.py::test_*_run_py_setup_beats_uniform_random's measurement, printed
 (greedy and uniform-random mean returns on 256 fresh scenarios) for a build:
-    python tools/learn_check.py [--lib exp/x.so] [--algo dqn|ppo] [--host-loop] [--seed S] [--steps N]"""
+    python tools/learn_check.py [--lib exp/x.so] [--algo dqn|ppo] [--host-loop] [--seed S] [--steps N]
+                                [--fused-rollout]"""
 import argparse
 import json
 import os
@@ -18,6 +19,7 @@ def main():
     ap.add_argument("--host-loop", action="store_true")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20000)
+    ap.add_argument("--fused-rollout", action="store_true", help="PPO: the rollout as one launch (lb_ppo_steps)")
     a = ap.parse_args()
     import torch  # noqa: F401  (before the library: one HIP runtime)
     from lbk8s import _native
@@ -35,11 +37,12 @@ def main():
     else:
         from lbk8s.ppo import PPO_DeepSets
         env = cli.get_env("loadbalancer", False, 6, 4, 24, "multi", num_envs=8, seed=0, monitor_file=None)
-        model = PPO_DeepSets(env, num_steps=100, n_minibatches=8, ent_coef=0.001, seed=a.seed)
+        model = PPO_DeepSets(env, num_steps=100, n_minibatches=8, ent_coef=0.001, seed=a.seed,
+                             fused_rollout=a.fused_rollout)
     model.learn(total_timesteps=a.steps)
     g, u = _greedy_vs_uniform(model.predict)
     print(json.dumps({"lib": os.path.basename(a.lib or "liblbk8s.so"), "algo": a.algo, "host_loop": a.host_loop,
-                      "seed": a.seed, "steps": a.steps, "greedy": g, "uniform": u, "margin": g - u}))
+                      "seed": a.seed, "steps": a.steps, "fused_rollout": bool(getattr(model, "fused_rollout", False)), "greedy": g, "uniform": u, "margin": g - u}))
 
 
 if __name__ == "__main__":

@@ -28,11 +28,19 @@ sys.path[:0] = [REPO, os.path.join(REPO, "gym-loadbalancing_amd")]
 
 from bench import CONFIGS  # noqa: E402
 
+# bench.py's scenarios and run.py's own training env (lbk8s.cli.env_kwargs: E = 6, no rejection,
+# multi reward, L = 100; with --envs 8 the reference's setup).  "default" (E = 8, rejection, R = 9)
+# and "run_py" have the one-launch PPO rollout's shape (--fused-rollout); config 4's E = 64 has not.
+RUN_PY = dict(num_nodes=24, num_zones=4, num_endpoints=6, rejection_allowed=False, arrival_rate_r=100,
+              call_duration_r=1, episode_length=100, reward_function="multi", latency_weight=1.0, cpu_weight=0.0,
+              gini_weight=0.0)
+RL_CONFIGS = dict(CONFIGS, run_py=RUN_PY)
+
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--algo", choices=("ppo", "dqn"), default="ppo")
-    ap.add_argument("--config", default=None, choices=sorted(CONFIGS))
+    ap.add_argument("--config", default=None, choices=sorted(RL_CONFIGS))
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--updates", type=int, default=2)
     ap.add_argument("--warmup-updates", type=int, default=1)
@@ -49,6 +57,9 @@ def parse():
     ap.add_argument("--fused-bookkeeping", action="store_true",
                     help="PPO: the rollout step's bookkeeping and GAE as one launch each "
                          "(PPO_DeepSets(fused_bookkeeping=True): lb_ppo_record, lb_gae)")
+    ap.add_argument("--fused-rollout", action="store_true",
+                    help="PPO: the rollout's vector steps as one launch (PPO_DeepSets(fused_rollout=True): "
+                         "lb_ppo_steps; --config default or run_py, not config 4's E = 64)")
     return ap.parse_args()
 
 
@@ -79,7 +90,7 @@ def main():
     dev = torch.device("cuda", local)
     B = args.envs
     name = args.config or ("e64_multi" if args.algo == "ppo" else "default")
-    env = LBVecEnv(B, device=dev, seed=0, env_id_offset=rank * B, as_tensors=True, **CONFIGS[name])
+    env = LBVecEnv(B, device=dev, seed=0, env_id_offset=rank * B, as_tensors=True, **RL_CONFIGS[name])
 
     def barrier_sync():
         torch.cuda.synchronize(dev)
@@ -97,8 +108,8 @@ def main():
         from lbk8s.ppo import PPO_DeepSets
         ppo = PPO_DeepSets(env, num_steps=args.num_steps, n_minibatches=8, update_epochs=4, ent_coef=0.001,
                            gamma=0.95, gae_lambda=0.97, seed=1, device=dev, fused_act=args.fused_act,
-                           fused_bookkeeping=args.fused_bookkeeping)
-        out.update(fused_act=ppo.fused_act, fused_bookkeeping=ppo.fused_bookkeeping)
+                           fused_bookkeeping=args.fused_bookkeeping, fused_rollout=args.fused_rollout)
+        out.update(fused_act=ppo.fused_act, fused_bookkeeping=ppo.fused_bookkeeping, fused_rollout=ppo.fused_rollout)
         next_obs = env.reset()
         next_done = torch.zeros(B, device=dev)
         for _ in range(args.warmup_updates):
@@ -119,7 +130,7 @@ def main():
         barrier_sync()
         wall = max_over_ranks(time.perf_counter() - t0)
         env_steps = args.updates * args.num_steps * B * world
-        out.update(metric="env-steps/s including PPO updates (config 4)", value=env_steps / wall,
+        out.update(metric=f"env-steps/s including PPO updates ({'config 4' if name == 'e64_multi' else name})", value=env_steps / wall,
                    unit="env-steps/s", updates=args.updates, num_steps=args.num_steps, minibatches=8, epochs=4,
                    ms_per_update=wall / args.updates * 1e3, rollout_ms=t_roll / args.updates * 1e3,
                    update_ms=t_upd / args.updates * 1e3,
