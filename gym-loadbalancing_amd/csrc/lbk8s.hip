@@ -27,6 +27,7 @@
 #include "lbk8s_ds_train.h"
 #include "lbk8s_dqn.h"
 #include "lbk8s_ppo.h"
+#include "lbk8s_eval.h"
 #include "lbk8s_slice.h"
 #include "lbk8s_tpe.h"
 #include "lbk8s_rollout.h"
@@ -1297,6 +1298,44 @@ int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_conf
     constexpr int P = 2;  // envs per wave iteration (the LDS budget: lbk8s_ppo.h)
     const unsigned grid = ds_grid_spread((num_envs + P - 1) / P);
     hipLaunchKernelGGL(k_ppo_steps<P>, dim3(grid), dim3(DS_BLOCK), 0, (hipStream_t)stream, d, e, r);
+    return check_launch();
+}
+
+// lb_eval_steps' shape is lb_ppo_steps' (the greedy forward in place of the sampling one)
+int lb_eval_steps_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    if (validate(cfg)) return 0;
+    return ppo_steps_fusable(cfg, num_envs, num_elements) ? 1 : 0;
+}
+
+int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* cfg, int64_t num_envs,
+                  int32_t num_elements, const uint8_t* masks, int32_t steps, int32_t* actions_all, float* rewards_all,
+                  uint8_t* dones_all, int32_t* actions_out, float* reward_out, uint8_t* done_out,
+                  double* ep_stats_out, double* ep_sum, double* ep_cnt, float* ret32, float* ep_r32, int64_t tag0,
+                  double* log, int64_t cap, uint32_t* count, void* stream) {
+    static_assert(2 * 16 <= DQN_OBS_F4, "the LDS observation image holds R <= 16 rows");
+    static_assert((VG_ACTOR + (DS_BLOCK / 64) * 2 * VG_SCRATCH) * 4 + (DS_BLOCK / 64) * 2 * 2 * DQN_OBS_F4 * 16 <=
+                      80 * 1024,
+                  "k_eval_steps<2>: two blocks per CU");
+    if (int r = validate(cfg)) return r;
+    if (num_envs < 1) return fail("lb_eval_steps: num_envs < 1");
+    if (steps < 1 || steps > LB_EVAL_STEPS_MAX) return fail("lb_eval_steps: steps must be in [1, 4096]");
+    if (!frag || !obs || !state || !actions_out || !reward_out || !done_out || !ep_stats_out)
+        return fail("lb_eval_steps: frag/obs/state/actions_out/reward_out/done_out/ep_stats_out NULL");
+    if ((ep_sum == nullptr) != (ep_cnt == nullptr)) return fail("lb_eval_steps: ep_sum and ep_cnt go together");
+    if (log && (!ret32 || !count || cap < 0)) return fail("lb_eval_steps: a log needs ret32, count and cap >= 0");
+    if (!ppo_steps_fusable(cfg, num_envs, num_elements))
+        return fail("lb_eval_steps: the env's shape has no one-launch evaluation (lb_eval_steps_supported)");
+    Params e = make_params(state, cfg, num_envs);
+    e.reward = reward_out;
+    e.done = done_out;
+    e.ep_stats = ep_stats_out;
+    DSParams d{nullptr, frag, nullptr, nullptr, num_envs, num_elements, 1, 0, nullptr, nullptr, nullptr, nullptr,
+               actions_out, masks};
+    EvalSteps r{steps, reinterpret_cast<float4*>(obs), actions_all, rewards_all, dones_all, ep_sum, ep_cnt,
+                ret32, ep_r32, tag0, log, cap, count};
+    constexpr int P = 2;  // envs per wave iteration, as dqn_steps_launch
+    const unsigned grid = ds_grid_spread((num_envs + P - 1) / P);
+    hipLaunchKernelGGL(k_eval_steps<P>, dim3(grid), dim3(DS_BLOCK), 0, (hipStream_t)stream, d, e, r);
     return check_launch();
 }
 

@@ -14,7 +14,8 @@ _PRODUCT_LIB = LIB_PATH
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 # csrc/Makefile's SRCS, in order: the library embeds the SHA-256 of their concatenation
 SOURCES = ("lbk8s.hip", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
-           "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "../../include/lbk8s.h",
+           "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "lbk8s_eval.h",
+           "../../include/lbk8s.h",
            "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_build.cpp")
 ABI_VERSION = 17
 
@@ -36,6 +37,7 @@ LB_EPLOG_W = 24
 LB_EPLOG_RET32, LB_EPLOG_REWARD, LB_EPLOG_ACTION, LB_EPLOG_ENV, LB_EPLOG_TAG = 16, 17, 18, 19, 20
 LB_STATUS_BAD_ACTION, LB_STATUS_NOT_RESET = 1, 2
 LB_PPO_STEPS_MAX = 4096  # lb_ppo_steps: vector steps per launch
+LB_EVAL_STEPS_MAX = 4096  # lb_eval_steps: vector steps per launch
 LB_GEOMETRY = {"auto": 0, "tpe": 1, "slice": 2}
 
 
@@ -224,6 +226,8 @@ def lib():
     L.lb_gae.argtypes = [vp] * 5 + [i64, i64, C.c_double, C.c_double, vp, vp, vp]
     L.lb_ppo_steps_supported.argtypes = [cfgp, i64, i32]
     L.lb_ppo_steps.argtypes = [vp, vp, vp, cfgp, i64, i32, i32, i32] + [vp] * 16 + [i64, vp, i64, vp, vp]
+    L.lb_eval_steps_supported.argtypes = [cfgp, i64, i32]
+    L.lb_eval_steps.argtypes = [vp, vp, vp, cfgp, i64, i32, vp, i32] + [vp] * 11 + [i64, vp, i64, vp, vp]
     L.lb_reward64.argtypes = [vp, cfgp, i64, C.POINTER(C.c_void_p)]
     L.lb_dqn_act.argtypes = [vp, vp, i64, i32, vp, vp, cfgp, C.POINTER(LBDQNExploreC), vp, vp]
     L.lb_dqn_step.argtypes = [vp, vp, i64, i32, vp, vp, cfgp, C.POINTER(LBDQNExploreC), vp, vp, vp, vp, vp, vp,
@@ -243,7 +247,7 @@ def lib():
               "lb_replay_sample", "lb_ds_set_grads", "lb_dqn_step", "lb_dqn_steps",
               "lb_dqn_steps_supported", "lb_ds_pack_pair", "lb_ds_forward_pair", "lb_ds_over_sets",
               "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample", "lb_ppo_record", "lb_gae",
-              "lb_ppo_steps_supported", "lb_ppo_steps"):
+              "lb_ppo_steps_supported", "lb_ppo_steps", "lb_eval_steps_supported", "lb_eval_steps"):
         getattr(L, f).restype = C.c_int
     v = L.lb_abi_version()
     if v != ABI_VERSION and product:
@@ -282,4 +286,5 @@ EXPORTED_SYMBOLS = ("lb_abi_version", "lb_last_error", "lb_validate_config", "lb
                     "lb_dqn_step",
                     "lb_dqn_steps", "lb_dqn_steps_supported", "lb_ds_pack_pair", "lb_ds_forward_pair",
                     "lb_ds_over_sets", "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample",
-                    "lb_ppo_record", "lb_gae", "lb_ppo_steps_supported", "lb_ppo_steps")
+                    "lb_ppo_record", "lb_gae", "lb_ppo_steps_supported", "lb_ppo_steps",
+                    "lb_eval_steps_supported", "lb_eval_steps")

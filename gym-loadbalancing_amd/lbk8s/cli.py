@@ -60,6 +60,9 @@ def build_parser():
     p.add_argument("--test_episodes", default=1, type=int, help="episodes played side by side by --testing")
     p.add_argument("--test_sequential", action="store_true",
                    help="--testing plays the episodes one after another on one env, as run_test_deepset.py")
+    p.add_argument("--test-fused", action="store_true",
+                   help="--testing plays its episodes in one launch (run_test(fused=True)) where the env's shape "
+                        "has it (E <= 16, R <= 16, fewer than 32,768 episodes); ignored with --test_sequential")
     p.add_argument("--device", default="cuda")
     p.add_argument("--seed", default=0, type=int, help="Philox seed of the envs")
     p.add_argument("--nproc", default=1, type=int, help="GPUs (ranks) to train on, one process each")
@@ -164,7 +167,8 @@ def main(argv=None):
             env = LBVecEnv(1, device=args.device, seed=args.seed, as_tensors=True, **kw)
             res = run_sequential(agent, args.test_episodes, env)
         else:
-            res = run_test(agent, n_episodes=args.test_episodes, seed=args.seed, device=args.device, **kw)
+            res = run_test(agent, n_episodes=args.test_episodes, seed=args.seed, device=args.device,
+                           fused=args.test_fused, **kw)
         result["test_returns"] = [float(r) for r in res["r"]]
     print(json.dumps(result))
     return result

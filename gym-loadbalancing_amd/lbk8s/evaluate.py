@@ -12,6 +12,8 @@ Two forms:
   masked argmax, the fused env step.  Auto-reset is off, so every env plays exactly one
   episode (episode_length steps).  Episode i is the scenario of global env id
   `env_id_offset + i` (Philox), so any single episode can be replayed alone.
+  With fused=True (the CLI's --test-fused) the whole episode is one launch (lb_eval_steps: the
+  argmax inside the forward kernel, the env in registers) where the env's shape has it.
 * run_sequential: the reference loop as written — ONE env, episodes one after another,
   DummyVecEnv's auto-reset on done followed by the loop's own reset() (so the auto-reset's
   scenario is drawn and discarded), VecMonitor's float32 episode return.  Pinned by
@@ -55,19 +57,57 @@ def greedy_actions(agent, obs, masks):
     return torch.argmax(scores, dim=1).to(torch.int32)
 
 
+def eval_image(agent, device):
+    """The actor-only weight image of a DeepSetAgent's actor or a DQNDeepSetAgent's Q network (the
+    same module) in a fixed buffer, as fused.q_argmax_graphable packs it: what lb_eval_steps reads.
+    Returns (the module, the image)."""
+    net = agent.actor if isinstance(agent, DeepSetAgent) else agent.q_network
+    frag = fused.pack_net_into(net.net, fused.frag_buffer(device))
+    return net, frag
+
+
 @torch.no_grad()
-def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", monitor_path=None, **env_kwargs):
+def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", monitor_path=None, fused=False,
+             return_trace=False, **env_kwargs):
     """Play n_episodes greedy episodes in parallel -> dict of per-episode numpy arrays:
-    "r" return, "l" length, the 12 numeric info keys of the final step, and "wall_s"."""
+    "r" return, "l" length, the 12 numeric info keys of the final step, and "wall_s".
+
+    fused: False, one forward, masked argmax and env step per time step, issued from Python; True,
+    the whole episode in one launch (LBVecEnv.eval_steps; ValueError where the shape has none);
+    None, the launch where it is supported, else the loop.  The launch takes the argmax inside
+    the forward kernel, the loop torch's argmax of the forward's scores: a float32 near-tie may
+    resolve differently.  return_trace: also "actions" / "rewards" / "dones" (L, n), every step's."""
     kw = dict(TEST_ENV)
     kw.update(env_kwargs)
     env = LBVecEnv(n_episodes, device=device, seed=seed, env_id_offset=env_id_offset, auto_reset=False,
                    as_tensors=True, **kw)
+    L = env.cfg.episode_length
+    if fused or fused is None:
+        why = _no_one_launch(agent, env)
+        if why and fused:
+            raise ValueError(f"run_test(fused=True): {why}")
+        fused = not why
     obs = env.reset()
     masks = env.action_masks()
-    t0 = time.time()
-    for _ in range(env.cfg.episode_length):
-        obs, _, _, _ = env.step(greedy_actions(agent, obs, masks))
+    trace = None
+    if return_trace:
+        trace = (torch.empty((L, n_episodes), dtype=torch.int32, device=env.device),
+                 torch.empty((L, n_episodes), dtype=torch.float32, device=env.device),
+                 torch.empty((L, n_episodes), dtype=torch.uint8, device=env.device))
+    if fused:
+        t0 = time.time()
+        _, frag = eval_image(agent, env.device)
+        # (every action is always valid: action_masks() is all True, so no mask is passed; eval_steps
+        # plays an episode longer than LB_EVAL_STEPS_MAX in launches of that many steps)
+        env.eval_steps(frag, obs, L, None, *(trace or ()))
+    else:
+        t0 = time.time()
+        for i in range(L):
+            obs, _, _, _ = env.step(greedy_actions(agent, obs, masks))
+            if trace is not None:
+                trace[0][i].copy_(env.actions)
+                trace[1][i].copy_(env.rewards)
+                trace[2][i].copy_(env.dones)
     st = env.stats().cpu().numpy()
     wall = time.time() - t0
     info = info_matrix(st, env.rewards.cpu().numpy(), env.actions.cpu().numpy())
@@ -76,7 +116,21 @@ def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", mo
         out[k] = info[:, j]
     if monitor_path is not None:
         write_monitor_csv(monitor_path, out, INFO_KEYS[:12])
+    if trace is not None:
+        out["actions"], out["rewards"] = trace[0].cpu().numpy(), trace[1].cpu().numpy()
+        out["dones"] = trace[2].cpu().numpy().astype(bool)
     return out
+
+
+def _no_one_launch(agent, env):
+    """Why run_test cannot play `env` with `agent` in one launch (None: it can)."""
+    net = (agent.actor if isinstance(agent, DeepSetAgent) else agent.q_network).net
+    if not fused._geometry_ok(net, env.obs):
+        return f"the fused forward does not cover this agent on {tuple(env.obs.shape)} observations"
+    if not env.eval_steps_supported(env.obs.shape[1]):
+        return (f"no one-launch evaluation for {env.num_envs} envs of {env.cfg.num_endpoints} endpoints "
+                "(eval_steps_supported: at most 16 observation rows, fewer than 32,768 envs)")
+    return None
 
 
 @torch.no_grad()

@@ -245,6 +245,17 @@ def pack_q_into(qnet, frag, bfrag=None):
     return frag
 
 
+def pack_net_into(net, frag):
+    """Pack the actor-only image of `net` (an EquivariantDeepSet's layers: a DQNDeepSetAgent's
+    q_network.net or a DeepSetAgent's actor.net, the same module) into the fixed image `frag`:
+    pack_q_into for either agent (one launch; graph-capturable)."""
+    w, keep = _weights_struct(net, None)
+    _native.check(_native.lib().lb_ds_pack(C.byref(w), frag.data_ptr(),
+                                           torch.cuda.current_stream(frag.device).cuda_stream))
+    del keep
+    return frag
+
+
 def bwd_frag_buffer(device):
     """A fixed backward weight-image buffer (pack_q_into's bfrag)."""
     return torch.empty(_native.LB_DS_BWD_FLOATS, dtype=torch.float32, device=device)

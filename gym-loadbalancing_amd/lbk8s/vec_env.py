@@ -496,6 +496,70 @@ class LBVecEnv:
                 if len(self._log_times) >= self._log_every:
                     self.flush_monitor()
 
+    def eval_steps_supported(self, R):
+        """Whether lb_eval_steps (a greedy evaluation's vector steps in one launch) covers this env
+        with R-row observations."""
+        return bool(self._L.lb_eval_steps_supported(C.byref(self._c), self.num_envs, R))
+
+    def eval_steps(self, frag, obs, steps, masks=None, actions_all=None, rewards_all=None, dones_all=None,
+                   ep_sum=None, ep_cnt=None):
+        """lb_eval_steps: `steps` greedy vector steps -- each the masked argmax of the actor-only
+        weight image `frag` on obs (fused.q_argmax_graphable's forward), step_device and, for a
+        monitored env or with ep_sum / ep_cnt, record_ppo's bookkeeping -- in one launch, bit for
+        bit those launches.  obs (B, R, 8) float32 is updated in place: it ends as the observations
+        after the last step.  masks (B, R) bool or None (all valid), fixed over the steps.  Step
+        i's actions / rewards / dones go to row i of actions_all (steps, B) int32 / rewards_all
+        (steps, B) float32 / dones_all (steps, B) uint8, each optional.  The env's own actions /
+        rewards / dones / ep_stats buffers end as the last step leaves them; ep_sum / ep_cnt (B,)
+        float64, both or neither, as record_ppo's.  A monitored env logs every step with its own
+        host time and flushes at record_ppo's cadence: the request is split into launches that end
+        where a flush is due.  Returns obs."""
+        t = self.torch
+        if not self._reset_called and not t.cuda.is_current_stream_capturing():
+            raise TypeError("step() called before reset()")
+        B, dev = self.num_envs, self.ep_stats.device
+        T = int(steps)
+        if T < 1:
+            raise ValueError("eval_steps: steps must be >= 1")
+        if not isinstance(obs, t.Tensor) or obs.dim() != 3:
+            raise ValueError("eval_steps: obs must be a (B, R, 8) tensor")
+        if (ep_sum is None) != (ep_cnt is None):
+            raise ValueError("eval_steps: ep_sum and ep_cnt go together")
+        R = obs.shape[1]
+        spec = [("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32, False), ("obs", obs, (B, R, 8), t.float32, False),
+                ("masks", masks, (B, R), t.bool, True), ("actions_all", actions_all, (T, B), t.int32, True),
+                ("rewards_all", rewards_all, (T, B), t.float32, True), ("dones_all", dones_all, (T, B), t.uint8, True),
+                ("ep_sum", ep_sum, (B,), t.float64, True), ("ep_cnt", ep_cnt, (B,), t.float64, True)]
+        for name, x, shape, dt, optional in spec:
+            if x is None and optional:
+                continue
+            if (not isinstance(x, t.Tensor) or x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous()
+                    or x.device != dev):
+                raise ValueError(f"eval_steps: {name} must be a contiguous {shape} {dt} tensor on {dev}")
+        if not self.eval_steps_supported(R):
+            raise RuntimeError("eval_steps: the env's shape has no one-launch evaluation (eval_steps_supported)")
+        i = 0
+        while i < T:
+            # a launch of steps i .. i + n - 1: the whole request, or up to the next flush
+            n = min(T - i, _native.LB_EVAL_STEPS_MAX)
+            if self.monitor:
+                n = min(n, self._log_every - len(self._log_times))
+            log = ((self._ptr(self._ret32), self._ptr(self._ep_r32), len(self._log_times), self._ptr(self._log), B,
+                    self._ptr(self._log_count)) if self.monitor else (None, None, 0, None, 0, None))
+            row = lambda x: self._ptr(x[i]) if x is not None else None
+            _native.check(self._L.lb_eval_steps(
+                self._ptr(frag), self._ptr(obs), self._ptr(self.state), C.byref(self._c), B, R, self._ptr(masks), n,
+                row(actions_all), row(rewards_all), row(dones_all), self._ptr(self.actions), self._ptr(self.rewards),
+                self._ptr(self.dones), self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt), *log,
+                self._stream()))
+            i += n
+            if self.monitor:
+                self._log_times.extend(time.time() for _ in range(n))
+                if len(self._log_times) >= self._log_every:
+                    self.flush_monitor()
+        self._host_cache = {}
+        return obs
+
     def flush_monitor(self):
         """Write the logged episodes (one host sync): in step order, env order within a step."""
         if not self.monitor or not self._log_times:

@@ -483,6 +483,49 @@ int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_conf
                  float* ret32, float* ep_r32, int64_t tag0, double* log, int64_t cap, uint32_t* count,
                  void* stream);
 
+/* ---- ABI 17, additions: a greedy evaluation's vector steps in ONE launch (the rebuild's
+ * run_test, run_test_deepset.py:44-98; as lb_dqn_steps is for a DQN train period and lb_ppo_steps
+ * for a PPO rollout).  Over an evaluation the network and the masks are fixed and every output is
+ * per env, so each wave takes its envs through all `steps` (1..LB_EVAL_STEPS_MAX) vector steps: the
+ * env in registers, the observations in LDS.  The call has exactly the effect, bit for bit, of
+ * running for i = 0 .. steps-1, with the same frag, state, cfg, masks and stream:
+ *   lb_ds_q_argmax(frag, obs, num_envs, num_elements, masks, q_out = NULL, actions_out)
+ *   lb_step(state, cfg, num_envs, actions_out, obs (<- the next observations), reward_out, done_out,
+ *           terminal_obs = NULL, ep_stats_out, trace = NULL)
+ *   lb_ppo_record(num_envs, done_out, ep_stats_out, next_done_out = scratch, ep_sum, ep_cnt, reward_out,
+ *                 the state's lb_reward64 array, actions_out, ret32, ep_r32, tag0 + i, log, cap, count)
+ * and of copying, after step i, actions_out / reward_out / done_out to row i of actions_all
+ * [steps][B] i32 / rewards_all [steps][B] f32 / dones_all [steps][B] u8 (B = num_envs; each of the
+ * three may be NULL independently: that trace is then not written).
+ * frag is an actor-only image (lb_ds_pack with NULL critic pointers): the Q network of a DQN agent
+ * or the actor of a PPO agent, the same module.  obs [B][R][8] is updated in place, as in
+ * lb_dqn_steps: it ends as the observations after the last step.  masks [B][R] u8 or NULL (all
+ * valid) are fixed over the launch.  actions_out, reward_out, done_out, ep_stats_out and the
+ * lb_reward64 array end as the last lb_step leaves them (an ep_stats row is written when its env's
+ * episode ends, at any step).  ep_sum / ep_cnt, ret32 / ep_r32 / log / cap / count: as lb_ppo_steps
+ * (log == NULL: no episode log, and those words are untouched; rows unordered within the call; rows
+ * past cap dropped but counted).  Both auto-reset settings of the state are covered (run_test
+ * plays with auto-reset off and steps == episode_length).
+ * No host synchronisation, no allocation, capturable in a HIP graph; arguments are checked on the
+ * host before any device call.
+ * Supported (lb_eval_steps_supported == 1; a property of the shape, never of the device; the same
+ * answer as lb_ppo_steps_supported): lb_dqn_steps' shape (the slice layout with 16 lanes per env:
+ * E <= 16 below 32,768 envs; num_elements <= 16) in Philox mode with num_elements the env's action
+ * count.
+ * Refused: num_envs < 1; steps outside [1, LB_EVAL_STEPS_MAX]; a NULL among frag, obs, state,
+ * actions_out, reward_out, done_out, ep_stats_out; one of ep_sum / ep_cnt alone; a log without
+ * ret32 or count, or with cap < 0; an unsupported shape (there is no fallback: ask
+ * lb_eval_steps_supported first). */
+#define LB_EVAL_STEPS_MAX 4096
+int lb_eval_steps_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements);
+int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* cfg,
+                  int64_t num_envs, int32_t num_elements, const uint8_t* masks, int32_t steps,
+                  int32_t* actions_all, float* rewards_all, uint8_t* dones_all,
+                  int32_t* actions_out, float* reward_out, uint8_t* done_out, double* ep_stats_out,
+                  double* ep_sum, double* ep_cnt,
+                  float* ret32, float* ep_r32, int64_t tag0, double* log, int64_t cap, uint32_t* count,
+                  void* stream);
+
 /* ---- Fused deep-sets training -----------------------------
  * Replaces the reference's autograd through the same modules in the PPO update
  * (envs/ppo_deepset.py:227-263 -> deep_sets_agent_original.py:56-106).  The training
