@@ -25,6 +25,7 @@
 #include "lbk8s_common.h"
 #include "lbk8s_deepsets.h"
 #include "lbk8s_ds_train.h"
+#include "lbk8s_steps.h"
 #include "lbk8s_dqn.h"
 #include "lbk8s_ppo.h"
 #include "lbk8s_eval.h"
@@ -146,34 +147,17 @@ struct EpLogParams {
 
 // one env's part of the episode log; every lane of the wave calls it (the ballot), live or not
 __device__ __forceinline__ void episode_log_env(const EpLogParams& p, int64_t env) {
-    const int lane = threadIdx.x & 63;
-    const bool live = env < p.B;
     bool d = false;
     float r32 = 0.f;
-    if (live) {
+    if (env < p.B) {
         // VecMonitor's float32 episode_returns += the env's float64 reward: one rounding
         r32 = p.reward64 ? (float)((double)p.ret32[env] + p.reward64[env]) : p.ret32[env] + p.reward[env];
         d = p.done[env] != 0;
         p.ret32[env] = d ? 0.f : r32;
         if (d && p.ep_r32) p.ep_r32[env] = r32;
     }
-    const uint64_t m = __ballot(d);
-    if (!m) return;
-    uint32_t base = 0;
-    if (lane == __ffsll((unsigned long long)m) - 1) base = atomicAdd(p.count, (uint32_t)__popcll(m));
-    base = (uint32_t)__shfl((int)base, __ffsll((unsigned long long)m) - 1);
-    if (!d) return;
-    const int64_t slot = (int64_t)base + __popcll(m & ((1ull << lane) - 1));
-    if (slot >= p.cap) return;
-    double* row = p.log + slot * LB_EPLOG_W;
-    const double* st = p.ep_stats + env * LB_ST_K;
-#pragma unroll
-    for (int k = 0; k < LB_ST_K; ++k) row[k] = st[k];
-    row[LB_EPLOG_RET32] = (double)r32;
-    row[LB_EPLOG_REWARD] = (double)p.reward[env];
-    row[LB_EPLOG_ACTION] = (double)p.actions[env];
-    row[LB_EPLOG_ENV] = (double)env;
-    row[LB_EPLOG_TAG] = (double)p.tag;
+    eplog_append(d, env, p.ep_stats, r32, p.tag, p.log, p.cap, p.count,
+                 [&] { return EpLogStep{p.reward[env], p.actions[env]}; });
 }
 
 __global__ __launch_bounds__(256) void k_episode_log(EpLogParams p) {
@@ -1009,6 +993,27 @@ unsigned ds_grid(int64_t groups) {
 // gets a block as soon as there are as many groups as CUs
 unsigned ds_grid_spread(int64_t groups) { return (unsigned)std::min<int64_t>(groups, device_cus()); }
 
+// The launch of a one-launch step kernel: a wave per group of STEPS_P envs.  2 puts the 4096-env
+// batch on every wave of the grid (4: half the waves idle; one env per wave measured slower:
+// profiles/r06_dqn_p1_ab.jsonl), and is what k_ppo_steps' LDS budget allows (lbk8s_ppo.h)
+constexpr int STEPS_P = 2;
+template <typename... A>
+int steps_launch(void (*kernel)(A...), int64_t num_envs, void* stream, A... args) {
+    const unsigned grid = ds_grid_spread((num_envs + STEPS_P - 1) / STEPS_P);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(DS_BLOCK), 0, (hipStream_t)stream, args...);
+    return check_launch();
+}
+
+// lb_ppo_steps' and lb_eval_steps' checks of their record arguments (fn: the entry point's name)
+int steps_record_check(const char* fn, const StepsRecord& rec) {
+    const char* msg = nullptr;
+    if ((rec.ep_sum == nullptr) != (rec.ep_cnt == nullptr)) msg = ": ep_sum and ep_cnt go together";
+    else if (rec.log && (!rec.ret32 || !rec.count || rec.cap < 0)) msg = ": a log needs ret32, count and cap >= 0";
+    if (!msg) return 0;
+    g_err = std::string(fn) + msg;
+    return -1;
+}
+
 // Which k_deepsets_fwd<TS, P, MODE, XR> (or k_ds_fwd_pair<1, P>) a forward takes: the one rule,
 // shared by ds_forward_launch, lb_ds_forward_pair and lb_ds_forward_kernel (which reports it).
 // ts == 0 is the chunked kernel (k_deepsets_fwd_big).
@@ -1200,10 +1205,7 @@ int dqn_steps_launch(const float* frag, float* obs, int64_t num_envs, int32_t nu
     DQNReplay r{slots, num_elements * 2, pos_in, pos_out, reinterpret_cast<float4*>(obs),
                 reinterpret_cast<float4*>(rb_obs), reinterpret_cast<float4*>(rb_next_obs), rb_actions, rb_rewards,
                 rb_dones, ep_sum, ep_cnt};
-    constexpr int P = 2;  // envs per wave iteration: 2 puts the 4096-env batch on every wave of the grid (4: half the waves idle)
-    const unsigned grid = ds_grid_spread((num_envs + P - 1) / P);
-    hipLaunchKernelGGL(k_dqn_step<P>, dim3(grid), dim3(DS_BLOCK), 0, (hipStream_t)stream, d, e, r, (int)steps, sync);
-    return check_launch();
+    return steps_launch(k_dqn_step<STEPS_P>, num_envs, stream, d, e, r, (int)steps, sync);
 }
 }  // namespace
 
@@ -1250,9 +1252,9 @@ int lb_dqn_steps(const float* frag, float* obs, int64_t num_envs, int32_t num_el
 }
 
 namespace {
-// lb_ppo_steps' shape: lb_dqn_step's one-launch shape (a property of the shape only), Philox draws
-// and a forward over exactly the env's actions
-bool ppo_steps_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+// lb_ppo_steps' and lb_eval_steps' shape: lb_dqn_step's one-launch shape (a property of the shape
+// only), Philox draws and a forward over exactly the env's actions
+bool steps_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
     const int32_t A = cfg->num_endpoints + (cfg->rejection_allowed ? 1 : 0);
     return num_envs >= 1 && cfg->rng_mode == LB_RNG_PHILOX && num_elements == A &&
            dqn_step_fusable(cfg, num_envs, num_elements);
@@ -1261,7 +1263,7 @@ bool ppo_steps_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_eleme
 
 int lb_ppo_steps_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
     if (validate(cfg)) return 0;
-    return ppo_steps_fusable(cfg, num_envs, num_elements) ? 1 : 0;
+    return steps_fusable(cfg, num_envs, num_elements) ? 1 : 0;
 }
 
 int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_config* cfg, int64_t num_envs,
@@ -1270,7 +1272,6 @@ int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_conf
                  float* last_done, int32_t* actions_out, uint8_t* done_out, double* ep_stats_out, double* ep_sum,
                  double* ep_cnt, float* ret32, float* ep_r32, int64_t tag0, double* log, int64_t cap, uint32_t* count,
                  void* stream) {
-    static_assert(2 * 16 <= DQN_OBS_F4, "the LDS observation image holds R <= 16 rows");
     if (int r = validate(cfg)) return r;
     if (num_envs < 1) return fail("lb_ppo_steps: num_envs < 1");
     if (steps < 1 || steps > LB_PPO_STEPS_MAX) return fail("lb_ppo_steps: steps must be in [1, 4096]");
@@ -1283,9 +1284,9 @@ int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_conf
     if (store_rows > 0 && (!obs_next || !dones_next)) return fail("lb_ppo_steps: obs_next / dones_next NULL");
     if (store_rows < steps && (!last_obs || !last_done))
         return fail("lb_ppo_steps: store_rows == steps - 1 needs last_obs and last_done");
-    if ((ep_sum == nullptr) != (ep_cnt == nullptr)) return fail("lb_ppo_steps: ep_sum and ep_cnt go together");
-    if (log && (!ret32 || !count || cap < 0)) return fail("lb_ppo_steps: a log needs ret32, count and cap >= 0");
-    if (!ppo_steps_fusable(cfg, num_envs, num_elements))
+    const StepsRecord rec{ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count};
+    if (int rc = steps_record_check("lb_ppo_steps", rec)) return rc;
+    if (!steps_fusable(cfg, num_envs, num_elements))
         return fail("lb_ppo_steps: the env's shape has no one-launch rollout (lb_ppo_steps_supported)");
     Params e = make_params(state, cfg, num_envs);
     e.done = done_out;
@@ -1293,18 +1294,14 @@ int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_conf
     DSParams d{nullptr, frag, nullptr, nullptr, num_envs, num_elements, 1, 1, nullptr, nullptr, nullptr, nullptr,
                actions_out, nullptr};
     PPOSteps r{steps, store_rows, obs, uniforms, actions_f32, logprobs, values, rewards,
-               reinterpret_cast<float4*>(obs_next), dones_next, reinterpret_cast<float4*>(last_obs), last_done,
-               ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count};
-    constexpr int P = 2;  // envs per wave iteration (the LDS budget: lbk8s_ppo.h)
-    const unsigned grid = ds_grid_spread((num_envs + P - 1) / P);
-    hipLaunchKernelGGL(k_ppo_steps<P>, dim3(grid), dim3(DS_BLOCK), 0, (hipStream_t)stream, d, e, r);
-    return check_launch();
+               reinterpret_cast<float4*>(obs_next), dones_next, reinterpret_cast<float4*>(last_obs), last_done, rec};
+    return steps_launch(k_ppo_steps<STEPS_P>, num_envs, stream, d, e, r);
 }
 
 // lb_eval_steps' shape is lb_ppo_steps' (the greedy forward in place of the sampling one)
 int lb_eval_steps_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
     if (validate(cfg)) return 0;
-    return ppo_steps_fusable(cfg, num_envs, num_elements) ? 1 : 0;
+    return steps_fusable(cfg, num_envs, num_elements) ? 1 : 0;
 }
 
 int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* cfg, int64_t num_envs,
@@ -1312,18 +1309,14 @@ int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* c
                   uint8_t* dones_all, int32_t* actions_out, float* reward_out, uint8_t* done_out,
                   double* ep_stats_out, double* ep_sum, double* ep_cnt, float* ret32, float* ep_r32, int64_t tag0,
                   double* log, int64_t cap, uint32_t* count, void* stream) {
-    static_assert(2 * 16 <= DQN_OBS_F4, "the LDS observation image holds R <= 16 rows");
-    static_assert((VG_ACTOR + (DS_BLOCK / 64) * 2 * VG_SCRATCH) * 4 + (DS_BLOCK / 64) * 2 * 2 * DQN_OBS_F4 * 16 <=
-                      80 * 1024,
-                  "k_eval_steps<2>: two blocks per CU");
     if (int r = validate(cfg)) return r;
     if (num_envs < 1) return fail("lb_eval_steps: num_envs < 1");
     if (steps < 1 || steps > LB_EVAL_STEPS_MAX) return fail("lb_eval_steps: steps must be in [1, 4096]");
     if (!frag || !obs || !state || !actions_out || !reward_out || !done_out || !ep_stats_out)
         return fail("lb_eval_steps: frag/obs/state/actions_out/reward_out/done_out/ep_stats_out NULL");
-    if ((ep_sum == nullptr) != (ep_cnt == nullptr)) return fail("lb_eval_steps: ep_sum and ep_cnt go together");
-    if (log && (!ret32 || !count || cap < 0)) return fail("lb_eval_steps: a log needs ret32, count and cap >= 0");
-    if (!ppo_steps_fusable(cfg, num_envs, num_elements))
+    const StepsRecord rec{ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count};
+    if (int rc = steps_record_check("lb_eval_steps", rec)) return rc;
+    if (!steps_fusable(cfg, num_envs, num_elements))
         return fail("lb_eval_steps: the env's shape has no one-launch evaluation (lb_eval_steps_supported)");
     Params e = make_params(state, cfg, num_envs);
     e.reward = reward_out;
@@ -1331,12 +1324,8 @@ int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* c
     e.ep_stats = ep_stats_out;
     DSParams d{nullptr, frag, nullptr, nullptr, num_envs, num_elements, 1, 0, nullptr, nullptr, nullptr, nullptr,
                actions_out, masks};
-    EvalSteps r{steps, reinterpret_cast<float4*>(obs), actions_all, rewards_all, dones_all, ep_sum, ep_cnt,
-                ret32, ep_r32, tag0, log, cap, count};
-    constexpr int P = 2;  // envs per wave iteration, as dqn_steps_launch
-    const unsigned grid = ds_grid_spread((num_envs + P - 1) / P);
-    hipLaunchKernelGGL(k_eval_steps<P>, dim3(grid), dim3(DS_BLOCK), 0, (hipStream_t)stream, d, e, r);
-    return check_launch();
+    EvalSteps r{steps, reinterpret_cast<float4*>(obs), actions_all, rewards_all, dones_all, rec};
+    return steps_launch(k_eval_steps<STEPS_P>, num_envs, stream, d, e, r);
 }
 
 int lb_dqn_head(const float* q, const float* q_next, const int64_t* actions, const float* rewards, const float* dones,

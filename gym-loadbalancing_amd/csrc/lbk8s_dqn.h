@@ -11,11 +11,12 @@
 // tail (profiles/r03_dqn_kernel_stats_setgrads.csv); here they follow the forward inside the
 // same waves.  Same functions, same order per env: bit for bit the three launches
 // (tests/test_gpu_dqn_step.py).  The launch takes P = 2 envs per wave iteration (lbk8s.hip:
-// dqn_steps_launch; one env per wave measured slower: profiles/r06_dqn_p1_ab.jsonl).
+// STEPS_P; one env per wave measured slower: profiles/r06_dqn_p1_ab.jsonl).  The per-group
+// skeleton it shares with k_ppo_steps and k_eval_steps is StepsGroup (lbk8s_steps.h).
 #pragma once
 
 #include "lbk8s_deepsets.h"
-#include "lbk8s_slice.h"
+#include "lbk8s_steps.h"
 
 namespace lbk {
 
@@ -48,7 +49,6 @@ struct DQNReplay {  // lb_replay_add's buffers
 // every block has read them: in and out may be the same words.  The counter wraps itself: the
 // last block's atomicInc (limit gridDim.x - 1) returns gridDim.x - 1 and stores 0, so a launch
 // that starts with *sync == 0 leaves it 0 with no separate store.
-constexpr int DQN_OBS_F4 = 34;  // float4s of an observation of R <= 17 rows (dqn_step_fusable: R <= 16)
 template <int P>
 __global__ __launch_bounds__(DS_BLOCK, 2) void k_dqn_step(DSParams d, Params e, DQNReplay r, int nsteps,
                                                          int32_t* sync) {
@@ -81,27 +81,17 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_dqn_step(DSParams d, Params e, 
     const int64_t nwaves = (int64_t)gridDim.x * NWB;
     const int R = d.R, col = lane & 15, grp = lane >> 4;
     const int64_t groups = (d.B + P - 1) / P, n4 = e.B * r.f4;
-    const int s = lane >> 4, l16 = lane & 15;
     // the group's observations across the launch's steps in LDS, two buffers (step i's input
     // and its next observations): the Q forward and the replay rows read them there, so a step
     // issues its stores and reads nothing back from global memory (round 6: each step waited
     // for its obs stores to land, then re-read them -- two memory round trips per step)
-    __shared__ __attribute__((aligned(16))) float4 OB[NWB][2][P * DQN_OBS_F4];
-    const int f4 = r.f4;  // float4s per observation (2 R <= DQN_OBS_F4: host check)
-    float4(*ob)[P * DQN_OBS_F4] = OB[threadIdx.x >> 6];
+    __shared__ __attribute__((aligned(16))) float4 OB[NWB][2][P * STEPS_OBS_F4];
+    float4(*ob)[P * STEPS_OBS_F4] = OB[threadIdx.x >> 6];
     for (int64_t gi = wave; gi < groups; gi += nwaves) {
-        const int64_t env0 = gi * P;
-        // the env held in registers across the launch's steps (as k_rollout_slice): loaded and
-        // observed once, its history counters and scalars stored after the last step
-        const int64_t env = env0 + s;
-        const bool live = s < P && env < e.B;
-        const int64_t j1 = (env0 + P < e.B ? env0 + P : e.B) * f4 - env0 * f4;  // the group's float4s
-        SEnv<1> v;
-        if (live) {
-            slice_load<16, 1>(e, env, l16, v);
-            slice_observe<1>(e, v);
-        }
-        for (int j = lane; j < j1; j += 64) ob[0][j] = r.obs[env0 * f4 + j];
+        StepsGroup<P> g;
+        g.open(e, nullptr, gi, lane, r.f4);  // (float4s per observation: 2 R <= STEPS_OBS_F4, host check)
+        const int64_t env0 = g.env0, env = g.env;
+        for (int j = lane; j < g.j1; j += 64) ob[0][j] = r.obs[env0 * g.f4 + j];
         for (int i = 0; i < nsteps; ++i) {
             const bool explore = (exm >> i) & 1u;
             const int64_t ps = (pos + i) % r.slots;
@@ -115,52 +105,39 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_dqn_step(DSParams d, Params e, 
                 ds_group_obs<1, P, 2>(d, env0, col, grp, R, h0, m0, xr0, reinterpret_cast<const float*>(cur));
                 act = ds_group_actor<1, P, 2, true>(d, W, lane, env0, col, grp, R, h0, m0, xs);
             }
-            const int32_t ag = __shfl(act, s < P ? s : 0);
-            // the env step: lanes 16 s .. 16 s + 15 step env env0 + s (k_step_slice<16, 1>'s body,
-            // the observed values kept in registers: a step changes the selected endpoint's)
+            const int32_t ag = __shfl(act, g.s < P ? g.s : 0);
             int a = 0;
-            float rw = 0.f;
-            bool dn = false;
-            double ret = 0.0;  // the finished episode's return (its ep_stats row's first column)
-            if (live) {
-                a = explore ? random_action(e, env, v.acc3, v.s.step) : ag;  // (exploring: :128-131)
-                if (explore && l16 == 0) d.actions[env] = a;
-                const SPrep pr = slice_prep<16, 1>(e, v, a);
-                const double tot0 = v.total;
-                const double reward = slice_apply<16, 1, false, false>(e, env, l16, v, pr, dn);
-                rw = (float)reward;
-                ret = e.auto_reset ? tot0 + reward : 0.0;  // (slice_apply's v.total += reward)
-                if (l16 == 0) {
-                    e.reward[env] = rw;
-                    if (e.rew64) e.rew64[env] = reward;
-                    e.done[env] = (uint8_t)dn;
-                }
-                slice_obs_rows<16, 1>(e, l16, v, [&](int q, float4 o) { nxt[s * f4 + q] = o; });
+            if (g.live) {
+                a = explore ? random_action(e, env, g.v.acc3, g.v.s.step) : ag;  // (exploring: :128-131)
+                if (explore && g.l16 == 0) d.actions[env] = a;
+            }
+            g.step(e, a, nxt);
+            if (g.head) {
+                e.reward[env] = g.rw;
+                if (e.rew64) e.rew64[env] = g.reward;
+                e.done[env] = (uint8_t)g.dn;
             }
             // the group's replay rows (lb_replay_add's) and obs <- next obs, from LDS (the
             // wave's LDS writes and reads complete in order)
-            for (int j = lane; j < j1; j += 64) {
+            for (int j = lane; j < g.j1; j += 64) {
                 const float4 o = cur[j], nx = nxt[j];
-                const int64_t g = env0 * f4 + j;
-                r.rb_obs[ps * n4 + g] = o;
-                r.rb_next_obs[ps * n4 + g] = nx;
-                r.obs[g] = nx;
-                st_stream(reinterpret_cast<float4*>(e.obs) + g, nx);
+                const int64_t q = env0 * g.f4 + j;
+                r.rb_obs[ps * n4 + q] = o;
+                r.rb_next_obs[ps * n4 + q] = nx;
+                r.obs[q] = nx;
+                st_stream(reinterpret_cast<float4*>(e.obs) + q, nx);
             }
-            if (live && l16 == 0) {  // (the lane that wrote the env's reward, done and stats row)
+            if (g.head) {  // (the lane that wrote the env's reward, done and stats row)
                 r.rb_actions[ps * e.B + env] = a;
-                r.rb_rewards[ps * e.B + env] = rw;
-                r.rb_dones[ps * e.B + env] = dn ? 1.f : 0.f;
-                if (r.ep_sum && dn) {
-                    r.ep_sum[env] += e.auto_reset ? ret : e.ep_stats[env * LB_ST_K];
+                r.rb_rewards[ps * e.B + env] = g.rw;
+                r.rb_dones[ps * e.B + env] = g.dn ? 1.f : 0.f;
+                if (r.ep_sum && g.dn) {
+                    r.ep_sum[env] += e.auto_reset ? g.ret : e.ep_stats[env * LB_ST_K];
                     r.ep_cnt[env] += 1.0;
                 }
             }
         }
-        if (live) {
-            if (l16 < e.E) e.edyn[eidx(e, env, l16)] = v.ed[0];
-            if (l16 == 0) slice_store_scalars<1>(e, env, v);
-        }
+        g.close(e, nullptr);
     }
     if (sync) {  // the last block to finish writes the device words (every block has read them)
         __shared__ int last;

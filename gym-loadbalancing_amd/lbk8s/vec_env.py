@@ -381,6 +381,46 @@ class LBVecEnv:
         self.state = None
 
     # ---- VecMonitor file ------------------------------------------------------------------------
+    def _check_tensors(self, who, spec):
+        """Each (name, tensor, shape, dtype, optional) of spec: a contiguous tensor of that shape and
+        dtype on the env's device, or None where optional."""
+        t, dev = self.torch, self.ep_stats.device
+        for name, x, shape, dt, optional in spec:
+            if x is None and optional:
+                continue
+            if (not isinstance(x, t.Tensor) or x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous()
+                    or x.device != dev):
+                raise ValueError(f"{who}: {name} must be a contiguous {shape} {dt} tensor on {dev}")
+
+    def _log_args(self):
+        """The episode-log arguments of a launch (ret32, ep_r32, its first step's tag, log, cap,
+        count); all empty for an env that is not monitored."""
+        if not self.monitor:
+            return (None, None, 0, None, 0, None)
+        return (self._ptr(self._ret32), self._ptr(self._ep_r32), len(self._log_times), self._ptr(self._log),
+                self.num_envs, self._ptr(self._log_count))
+
+    def _logged(self, n=1):
+        """n vector steps were logged: their host times, and the flush when it is due."""
+        if not self.monitor:
+            return
+        self._log_times.extend(time.time() for _ in range(n))
+        if len(self._log_times) >= self._log_every:
+            self.flush_monitor()
+
+    def _launches(self, T, most):
+        """(i, n) of the launches of a request of T steps, at most `most` each: launch i .. i + n - 1
+        is the rest of the request, or ends where a flush is due (the caller reports each launch
+        with _logged(n); within that many steps an env finishes at most once, so the log cannot
+        overflow)."""
+        i = 0
+        while i < T:
+            n = min(T - i, most)
+            if self.monitor:
+                n = min(n, self._log_every - len(self._log_times))
+            yield i, n
+            i += n
+
     def record_episodes(self, dones=None, rewards=None, actions=None):
         """VecMonitor bookkeeping of the last vector step, on the device: the float32 running
         returns and, for the finished envs only, their rows appended to the episode log
@@ -394,11 +434,8 @@ class LBVecEnv:
         a = self.actions if actions is None else actions
         _native.check(self._L.lb_episode_log(
             self.num_envs, self._ptr(d), self._ptr(self.ep_stats), self._ptr(r), self._rew64, self._ptr(a),
-            self._ptr(self._ret32), self._ptr(self._ep_r32), len(self._log_times), self._ptr(self._log),
-            self.num_envs, self._ptr(self._log_count), self._stream()))
-        self._log_times.append(time.time())
-        if len(self._log_times) >= self._log_every:
-            self.flush_monitor()
+            *self._log_args(), self._stream()))
+        self._logged()
 
     def record_ppo(self, dones, rewards, actions, next_done_out, ep_sum, ep_cnt):
         """PPO's bookkeeping of the last vector step in one launch (lb_ppo_record): the done
@@ -408,26 +445,16 @@ class LBVecEnv:
         and the flush cadence) when the env is monitored; no log otherwise."""
         t = self.torch
         B = self.num_envs
-        for name, x, dt in (("dones", dones, t.uint8), ("rewards", rewards, t.float32), ("actions", actions, t.int32),
-                            ("next_done_out", next_done_out, t.float32), ("ep_sum", ep_sum, t.float64),
-                            ("ep_cnt", ep_cnt, t.float64)):
-            if (not isinstance(x, t.Tensor) or x.dtype != dt or tuple(x.shape) != (B,) or not x.is_contiguous()
-                    or x.device != self.ep_stats.device):
-                raise ValueError(f"record_ppo: {name} must be a contiguous ({B},) {dt} tensor on "
-                                 f"{self.ep_stats.device}")
-        head = (B, self._ptr(dones), self._ptr(self.ep_stats), self._ptr(next_done_out), self._ptr(ep_sum),
-                self._ptr(ep_cnt))
-        if not self.monitor:
-            _native.check(self._L.lb_ppo_record(*head, None, None, None, None, None, 0, None, 0, None,
-                                                self._stream()))
-            return
+        self._check_tensors("record_ppo", [
+            (name, x, (B,), dt, False)
+            for name, x, dt in (("dones", dones, t.uint8), ("rewards", rewards, t.float32),
+                                ("actions", actions, t.int32), ("next_done_out", next_done_out, t.float32),
+                                ("ep_sum", ep_sum, t.float64), ("ep_cnt", ep_cnt, t.float64))])
+        step = (self._ptr(rewards), self._rew64, self._ptr(actions)) if self.monitor else (None, None, None)
         _native.check(self._L.lb_ppo_record(
-            *head, self._ptr(rewards), self._rew64, self._ptr(actions), self._ptr(self._ret32),
-            self._ptr(self._ep_r32), len(self._log_times), self._ptr(self._log), B, self._ptr(self._log_count),
-            self._stream()))
-        self._log_times.append(time.time())
-        if len(self._log_times) >= self._log_every:
-            self.flush_monitor()
+            B, self._ptr(dones), self._ptr(self.ep_stats), self._ptr(next_done_out), self._ptr(ep_sum),
+            self._ptr(ep_cnt), *step, *self._log_args(), self._stream()))
+        self._logged()
 
     def ppo_steps_supported(self, R):
         """Whether lb_ppo_steps (a PPO rollout's vector steps in one launch) covers this env with
@@ -449,7 +476,7 @@ class LBVecEnv:
         t = self.torch
         if not self._reset_called and not t.cuda.is_current_stream_capturing():
             raise TypeError("step() called before reset()")
-        B, dev = self.num_envs, self.ep_stats.device
+        B = self.num_envs
         if not isinstance(uniforms, t.Tensor) or uniforms.dim() != 2 or uniforms.shape[0] < 1:
             raise ValueError("ppo_steps: uniforms must be a (T, B) tensor with T >= 1")
         if not isinstance(obs, t.Tensor) or obs.dim() != 3:
@@ -458,43 +485,29 @@ class LBVecEnv:
         S = obs_next.shape[0] if isinstance(obs_next, t.Tensor) and obs_next.dim() == 4 else -1
         if S not in (T, T - 1):
             raise ValueError(f"ppo_steps: obs_next must be a ({T} or {T - 1}, {B}, {R}, 8) tensor")
-        spec = [("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32), ("obs", obs, (B, R, 8), t.float32),
-                ("uniforms", uniforms, (T, B), t.float32), ("actions_f32", actions_f32, (T, B), t.float32),
-                ("logprobs", logprobs, (T, B), t.float32), ("values", values, (T, B), t.float32),
-                ("rewards", rewards, (T, B), t.float32), ("obs_next", obs_next, (S, B, R, 8), t.float32),
-                ("dones_next", dones_next, (S, B), t.float32), ("actions", actions, (B,), t.int32),
-                ("dones", dones, (B,), t.uint8), ("ep_sum", ep_sum, (B,), t.float64),
-                ("ep_cnt", ep_cnt, (B,), t.float64)]
-        if S < T or last_obs is not None or last_done is not None:
-            spec += [("last_obs", last_obs, (B, R, 8), t.float32), ("last_done", last_done, (B,), t.float32)]
-        for name, x, shape, dt in spec:
-            if (not isinstance(x, t.Tensor) or x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous()
-                    or x.device != dev):
-                raise ValueError(f"ppo_steps: {name} must be a contiguous {shape} {dt} tensor on {dev}")
+        last = S == T and last_obs is None and last_done is None  # (last_* optional: every row is stored)
+        self._check_tensors("ppo_steps", [
+            ("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32, False), ("obs", obs, (B, R, 8), t.float32, False),
+            ("uniforms", uniforms, (T, B), t.float32, False), ("actions_f32", actions_f32, (T, B), t.float32, False),
+            ("logprobs", logprobs, (T, B), t.float32, False), ("values", values, (T, B), t.float32, False),
+            ("rewards", rewards, (T, B), t.float32, False), ("obs_next", obs_next, (S, B, R, 8), t.float32, False),
+            ("dones_next", dones_next, (S, B), t.float32, False), ("actions", actions, (B,), t.int32, False),
+            ("dones", dones, (B,), t.uint8, False), ("ep_sum", ep_sum, (B,), t.float64, False),
+            ("ep_cnt", ep_cnt, (B,), t.float64, False), ("last_obs", last_obs, (B, R, 8), t.float32, last),
+            ("last_done", last_done, (B,), t.float32, last)])
         if not self.ppo_steps_supported(R):
             raise RuntimeError("ppo_steps: the env's shape has no one-launch rollout (ppo_steps_supported)")
-        i = 0
-        while i < T:
-            # a launch of steps i .. i + n - 1: the whole request, or up to the next flush
-            n = min(T - i, _native.LB_PPO_STEPS_MAX)
-            if self.monitor:
-                n = min(n, self._log_every - len(self._log_times))
+        for i, n in self._launches(T, _native.LB_PPO_STEPS_MAX):
             s = min(n, S - i)  # rows of obs_next / dones_next this launch fills (n, or n - 1 at the end)
             src = obs if i == 0 else obs_next[i - 1]
-            log = ((self._ptr(self._ret32), self._ptr(self._ep_r32), len(self._log_times), self._ptr(self._log), B,
-                    self._ptr(self._log_count)) if self.monitor else (None, None, 0, None, 0, None))
             _native.check(self._L.lb_ppo_steps(
                 self._ptr(frag), self._ptr(src), self._ptr(self.state), C.byref(self._c), B, R, n, s,
                 self._ptr(uniforms[i]), self._ptr(actions_f32[i]), self._ptr(logprobs[i]), self._ptr(values[i]),
                 self._ptr(rewards[i]), self._ptr(obs_next[i]) if s else None,
                 self._ptr(dones_next[i]) if s else None, self._ptr(last_obs) if s < n else None,
                 self._ptr(last_done) if s < n else None, self._ptr(actions), self._ptr(dones),
-                self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt), *log, self._stream()))
-            i += n
-            if self.monitor:
-                self._log_times.extend(time.time() for _ in range(n))
-                if len(self._log_times) >= self._log_every:
-                    self.flush_monitor()
+                self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt), *self._log_args(), self._stream()))
+            self._logged(n)
 
     def eval_steps_supported(self, R):
         """Whether lb_eval_steps (a greedy evaluation's vector steps in one launch) covers this env
@@ -517,7 +530,7 @@ class LBVecEnv:
         t = self.torch
         if not self._reset_called and not t.cuda.is_current_stream_capturing():
             raise TypeError("step() called before reset()")
-        B, dev = self.num_envs, self.ep_stats.device
+        B = self.num_envs
         T = int(steps)
         if T < 1:
             raise ValueError("eval_steps: steps must be >= 1")
@@ -526,37 +539,21 @@ class LBVecEnv:
         if (ep_sum is None) != (ep_cnt is None):
             raise ValueError("eval_steps: ep_sum and ep_cnt go together")
         R = obs.shape[1]
-        spec = [("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32, False), ("obs", obs, (B, R, 8), t.float32, False),
-                ("masks", masks, (B, R), t.bool, True), ("actions_all", actions_all, (T, B), t.int32, True),
-                ("rewards_all", rewards_all, (T, B), t.float32, True), ("dones_all", dones_all, (T, B), t.uint8, True),
-                ("ep_sum", ep_sum, (B,), t.float64, True), ("ep_cnt", ep_cnt, (B,), t.float64, True)]
-        for name, x, shape, dt, optional in spec:
-            if x is None and optional:
-                continue
-            if (not isinstance(x, t.Tensor) or x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous()
-                    or x.device != dev):
-                raise ValueError(f"eval_steps: {name} must be a contiguous {shape} {dt} tensor on {dev}")
+        self._check_tensors("eval_steps", [
+            ("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32, False), ("obs", obs, (B, R, 8), t.float32, False),
+            ("masks", masks, (B, R), t.bool, True), ("actions_all", actions_all, (T, B), t.int32, True),
+            ("rewards_all", rewards_all, (T, B), t.float32, True), ("dones_all", dones_all, (T, B), t.uint8, True),
+            ("ep_sum", ep_sum, (B,), t.float64, True), ("ep_cnt", ep_cnt, (B,), t.float64, True)])
         if not self.eval_steps_supported(R):
             raise RuntimeError("eval_steps: the env's shape has no one-launch evaluation (eval_steps_supported)")
-        i = 0
-        while i < T:
-            # a launch of steps i .. i + n - 1: the whole request, or up to the next flush
-            n = min(T - i, _native.LB_EVAL_STEPS_MAX)
-            if self.monitor:
-                n = min(n, self._log_every - len(self._log_times))
-            log = ((self._ptr(self._ret32), self._ptr(self._ep_r32), len(self._log_times), self._ptr(self._log), B,
-                    self._ptr(self._log_count)) if self.monitor else (None, None, 0, None, 0, None))
+        for i, n in self._launches(T, _native.LB_EVAL_STEPS_MAX):
             row = lambda x: self._ptr(x[i]) if x is not None else None
             _native.check(self._L.lb_eval_steps(
                 self._ptr(frag), self._ptr(obs), self._ptr(self.state), C.byref(self._c), B, R, self._ptr(masks), n,
                 row(actions_all), row(rewards_all), row(dones_all), self._ptr(self.actions), self._ptr(self.rewards),
-                self._ptr(self.dones), self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt), *log,
-                self._stream()))
-            i += n
-            if self.monitor:
-                self._log_times.extend(time.time() for _ in range(n))
-                if len(self._log_times) >= self._log_every:
-                    self.flush_monitor()
+                self._ptr(self.dones), self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt),
+                *self._log_args(), self._stream()))
+            self._logged(n)
         self._host_cache = {}
         return obs
 
