@@ -24,6 +24,7 @@ episodes (one 2-double all_reduce per log line).
 import os
 import random
 import time
+from contextlib import contextmanager
 from copy import deepcopy
 
 import numpy as np
@@ -33,7 +34,8 @@ from torch import optim
 
 from . import _native, fused, fused_train
 from . import dist as lbdist
-from .deepsets import DQNDeepSetAgent, HUGE_NEG, allreduce_gradients
+from .deepsets import DQNDeepSetAgent, HUGE_NEG
+from .train_step import TrainStep
 
 
 DQN_STEPS_MAX = 32  # lb_dqn_steps' longest launch (include/lbk8s.h)
@@ -180,8 +182,8 @@ class DQN_DeepSets:
                                     fused=(self.device.type == "cuda" and os.environ.get("LBK8S_FUSED_ADAM", "1") == "1")
                                     or None, capturable=self.train_graph)
         self._multi = lbdist.is_multi()
-        self._gflat = torch.zeros(sum(p.numel() for p in self.q_network.parameters()), device=self.device) \
-            if self._multi else None
+        # backward -> [gradient all_reduce] -> Adam, eager or captured
+        self._ts = TrainStep(self.q_network, self.optimizer, self.device)
         self._tgraphs = None
         self.rb = DeviceReplayBuffer(buffer_size, self.num_envs, env.observation_space.shape, self.device, self.gen)
         self._act = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
@@ -231,7 +233,6 @@ class DQN_DeepSets:
         # the q network's training-backward image, packed with its forward image at the start
         # of every train period (lb_ds_pack_pair) and pinned for the run
         self._qbfrag = fused.bwd_frag_buffer(self.device) if self.device_rng else None
-        self._one = None
 
     def select_actions(self, obs, masks, epsilon):
         if random.random() < epsilon:  # one draw decides exploration for every env (:127)
@@ -309,8 +310,7 @@ class DQN_DeepSets:
         """lb_replay_sample into the train step's fixed buffers; the counter is the vector step
         word of `parity` (the step count after the period's last step)."""
         rb, B = self.rb, self.batch_size
-        if self._tstatic is None:
-            self._alloc_tstatic()
+        self._alloc_tstatic()
         o, a, no, d, r = self._tstatic
         vp = self._vstep_pp.data_ptr() + 8 * parity
         _native.check(_native.lib().lb_replay_sample(
@@ -320,8 +320,8 @@ class DQN_DeepSets:
             d.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
 
     def _period_body(self, obs, masks, n, train, parity):
-        """n vector steps from `parity` then (train) the sample and the train step; returns
-        the graphs' split point for the all_reduce (multi-rank) via self._period_split."""
+        """n vector steps from `parity` then (train) the sample and the train step's backward
+        (its loss in self._tloss); the caller applies the step, after the all_reduce."""
         # (with the train step, its backward's image of the same weights in the same launch)
         fused.pack_q_into(self.q_network, self._qfrag, self._qbfrag if train else None)
         self._vector_steps_dev(obs, masks, parity, n)
@@ -336,13 +336,15 @@ class DQN_DeepSets:
         """Capture the period graphs: keys (n, train, parity, reps) for n in {1, train_frequency};
         reps > 1: that many consecutive train periods in one graph (single rank)."""
         F = self.train_frequency
-        if self._tstatic is None:
-            self._alloc_tstatic()
-        # only the torch part needs a warm-up (its allocations); the vector steps and the
-        # sample are native launches on fixed buffers, captured without running them, so the
-        # env, the replay and the step counter are untouched and a graphed learn() follows
-        # the same trajectory as an eager one
-        self._train_warmup()
+        self._alloc_tstatic()
+        # only the torch part needs a warm-up (its allocations; undone, and nothing is drawn);
+        # the vector steps and the sample are native launches on fixed buffers, captured
+        # without running them, so the env, the replay and the step counter are untouched and
+        # a graphed learn() follows the same trajectory as an eager one.  (The period graphs
+        # are rebuilt whenever a learn() changes the exploration slope; training continues
+        # from the same optimizer state.)
+        self._ts.warmup(lambda: self._train_backward(*self._tstatic))
+        fused.invalidate(self.q_network)
         graphs = {}
         keys = {(1, False, 1), (F, False, 1), (F, True, 1), (F, True, self._reps())}
         for n, train, reps in sorted(keys):
@@ -354,13 +356,13 @@ class DQN_DeepSets:
                     for _ in range(reps):
                         self._period_body(obs, masks, n, train, p)
                         if train and not self._multi:
-                            self._train_apply()
+                            self._ts.apply()
                         p ^= n & 1
                 gs = (ga,)
                 if train and self._multi:
                     gb = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gb):
-                        self._train_apply()
+                        self._ts.apply()
                     gs = (ga, gb)
                 # (each graph writes its own loss tensor: the last period's)
                 graphs[n, train, parity, reps] = (gs, self._tloss)
@@ -384,6 +386,9 @@ class DQN_DeepSets:
         return R
 
     def _alloc_tstatic(self):
+        """The train step's fixed sample buffers (obs, actions, next_obs, dones, rewards), once."""
+        if self._tstatic is not None:
+            return
         B, rb = self.batch_size, self.rb
         obs_shape = tuple(rb.obs.shape[2:])
         self._tstatic = (torch.zeros((B,) + obs_shape, device=self.device),
@@ -391,45 +396,46 @@ class DQN_DeepSets:
                          torch.zeros((B,) + obs_shape, device=self.device),
                          torch.zeros((B, 1), device=self.device), torch.zeros((B, 1), device=self.device))
 
-    def _train_warmup(self):
-        """Two train steps on a side stream (grads, Adam state, workspaces allocated before a
-        capture), then the parameters and the Adam state (moments and step counter) restored
-        to their values before the warm-up: nothing is drawn.  (The period graphs are rebuilt
-        whenever a learn() changes the exploration slope; training continues from the same
-        optimizer state.)"""
-        params = list(self.q_network.parameters())
-        snap = [p.detach().clone() for p in params]
-        opt_snap = self._snapshot_optimizer()
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._train_backward(*self._tstatic)
-                self._allreduce()
-                self._train_apply()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        with torch.no_grad():
-            for p, q in zip(params, snap):
-                p.copy_(q)
-        self._restore_optimizer(opt_snap)
-        fused.invalidate(self.q_network)
-
-    def _after_train(self, global_step):
+    def _after_train(self, global_step, pack_target):
+        """The bookkeeping after an optimizer step; pack_target (the device loop): a changed
+        target network's pinned image is packed anew."""
+        # the fused forward's cached weight image of the q network is stale now: neither a
+        # replayed Adam step nor torch's fused Adam kernel moves the version counters it keys on
         fused.invalidate(self.q_network)
         self.train_steps += 1
         if global_step % self.target_network_frequency == 0:
+            # (dqn_deepset.py:199-203) in place on the parameters themselves, so their version
+            # counters move and the fused forward's cached weight image of the target is rebuilt
+            # (writes through .data would leave that image stale)
             with torch.no_grad():
                 for tp, qp in zip(self.target_network.parameters(), self.q_network.parameters()):
                     tp.copy_(self.tau * qp + (1.0 - self.tau) * tp)
             fused.invalidate(self.target_network)
-            fused.pack_q_into(self.target_network, self._tfrag)
+            if pack_target:
+                fused.pack_q_into(self.target_network, self._tfrag)
+
+    @contextmanager
+    def _pinned_images(self):
+        """The device loop's fixed weight images (the q network's forward and backward images,
+        the target's forward image) stand for the networks' cached ones inside the block."""
+        fused.pin(self.q_network, self._qfrag)
+        fused.pin(self.target_network, self._tfrag)
+        fused.pin_backward(self.q_network, self._qbfrag)
+        try:
+            yield
+        finally:
+            fused.pin(self.q_network, None)
+            fused.pin(self.target_network, None)
+            fused.pin_backward(self.q_network, None)
+            fused.invalidate(self.q_network)
+            fused.invalidate(self.target_network)
 
     def _learn_device(self, total_timesteps):
         """learn() with device RNG: one graph replay per train period (period_graph) or the
         same kernels eagerly."""
         env = self.env
         start = time.time()
-        obs, masks = self._obs, self._masks
+        obs = self._obs
         slope = self._set_schedule(total_timesteps)
         env.reset()
         obs.copy_(env.obs)
@@ -438,17 +444,8 @@ class DQN_DeepSets:
         # target's when the target changes
         fused.pack_q_into(self.q_network, self._qfrag, self._qbfrag)
         fused.pack_q_into(self.target_network, self._tfrag)
-        fused.pin(self.q_network, self._qfrag)
-        fused.pin(self.target_network, self._tfrag)
-        fused.pin_backward(self.q_network, self._qbfrag)
-        try:
+        with self._pinned_images():
             return self._learn_device_loop(total_timesteps, start, slope)
-        finally:
-            fused.pin(self.q_network, None)
-            fused.pin(self.target_network, None)
-            fused.pin_backward(self.q_network, None)
-            fused.invalidate(self.q_network)
-            fused.invalidate(self.target_network)
 
     def prepare(self, total_timesteps):
         """Capture the period graphs of a learn(total_timesteps) (its exploration slope) without
@@ -459,18 +456,9 @@ class DQN_DeepSets:
         slope = self._set_schedule(total_timesteps)
         if self._pgraphs and self._pgraph_slope == slope:
             return
-        fused.pin(self.q_network, self._qfrag)
-        fused.pin(self.target_network, self._tfrag)
-        fused.pin_backward(self.q_network, self._qbfrag)
-        try:
+        with self._pinned_images():
             self._pgraphs = self._build_period_graphs(self._obs, self._masks)
             self._pgraph_slope = slope
-        finally:
-            fused.pin(self.q_network, None)
-            fused.pin(self.target_network, None)
-            fused.pin_backward(self.q_network, None)
-            fused.invalidate(self.q_network)
-            fused.invalidate(self.target_network)
 
     def _learn_device_loop(self, total_timesteps, start, slope):
         env = self.env
@@ -503,32 +491,26 @@ class DQN_DeepSets:
                     train = last > self.learning_starts and last % F == 0
                     hit = self._pgraphs[n, train, self._parity, reps]
                 gs, tloss = hit
-                gs[0].replay()
-                if len(gs) > 1:
-                    self._allreduce()  # eager collective on the current stream, between the two graphs
-                    gs[1].replay()
+                self._ts.replay(gs)
                 if train:
                     loss = tloss
                 for _ in range(reps - 1):  # (the chunk's earlier periods: the host mirror)
                     for _ in range(n):
                         self._parity ^= 1
                         self.rb.advance_host()
-                    self._after_train(last)
+                    self._after_train(last, True)
                     g, last = g + n, last + n
             else:
                 self._period_body(obs, masks, n, train, self._parity)
                 if train:
-                    if self._multi and not self.train_graph:
-                        allreduce_gradients(self.q_network)
-                    else:
-                        self._allreduce()
-                    self._train_apply()
+                    self._ts.allreduce()
+                    self._ts.apply()
                     loss = self._tloss
             for _ in range(n):
                 self._parity ^= 1
                 self.rb.advance_host()
             if train:
-                self._after_train(last)
+                self._after_train(last, True)
             marks = [s for s in range(g, last + 1) if s % 1000 == 0 or s == total_timesteps - 1]
             if marks:
                 # (logged at the 1000-step boundary inside the period, as the host loop logs it;
@@ -564,121 +546,29 @@ class DQN_DeepSets:
         return graphs
 
     def _train_backward(self, obs, actions, next_obs, dones, rewards):
-        """dqn_deepset.py:180-190: TD loss and its gradients; with several ranks the gradients
-        end packed in the flat bucket that the all_reduce averages."""
+        """dqn_deepset.py:180-190: TD loss and its gradients (several ranks: in the bucket)."""
         loss, _, _ = dqn_loss(self.q_network, self.target_network, obs, actions, next_obs, rewards, dones,
                               self.gamma)
-        # (also inside a captured step: autograd then allocates the gradients from the graph's
-        # pool, at the same addresses every replay, and no zero fill + accumulate per parameter
-        # is recorded)
-        self.optimizer.zero_grad(set_to_none=True)
-        # (the seed gradient from a fixed tensor: loss.backward() fills a new one each step)
-        if self._one is None or self._one.device != loss.device:
-            self._one = fused_train.unit_seed(loss.device, loss.dtype)
-        loss.backward(self._one)
-        if self._multi and self.train_graph:
-            torch.cat([p.grad.reshape(-1) for p in self.q_network.parameters()], out=self._gflat)
+        self._ts.backward(loss)
         return loss
-
-    def _train_apply(self):
-        if self._multi and self.train_graph:
-            self._gflat /= torch.distributed.get_world_size()
-            off = 0
-            for p in self.q_network.parameters():
-                n = p.numel()
-                p.grad.copy_(self._gflat[off:off + n].view_as(p))
-                off += n
-        self.optimizer.step()
-
-    def _capture_train(self):
-        """Capture the train step on fixed sample buffers: one graph on one rank, two graphs
-        around the gradient all_reduce on several (as PPO's minibatch step).  The warm-up
-        steps are undone (parameters and Adam state restored) and draw nothing from the
-        sampling generator, so a graphed run trains exactly as an eager one."""
-        B, rb = self.batch_size, self.rb
-        obs_shape = tuple(rb.obs.shape[2:])
-        self._tstatic = (torch.zeros((B,) + obs_shape, device=self.device),
-                         torch.zeros((B, 1), dtype=torch.long, device=self.device),
-                         torch.zeros((B,) + obs_shape, device=self.device),
-                         torch.zeros((B, 1), device=self.device), torch.zeros((B, 1), device=self.device))
-        params = list(self.q_network.parameters())
-        snap = [p.detach().clone() for p in params]
-        opt_snap = self._snapshot_optimizer()
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up: allocates grads, Adam state, workspaces
-                self._train_backward(*self._tstatic)
-                self._allreduce()
-                self._train_apply()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        if self._multi:
-            ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ga):
-                self._tloss = self._train_backward(*self._tstatic)
-            with torch.cuda.graph(gb):
-                self._train_apply()
-            self._tgraphs = (ga, gb)
-        else:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._tloss = self._train_backward(*self._tstatic)
-                self._train_apply()
-            self._tgraphs = (g,)
-        with torch.no_grad():
-            for p, q in zip(params, snap):
-                p.copy_(q)
-        self._restore_optimizer(opt_snap)
-        fused.invalidate(self.q_network)
-
-    def _snapshot_optimizer(self):
-        """Copies of the Adam state tensors (moments, step) by parameter, before a warm-up."""
-        return {id(p): {k: v.detach().clone() for k, v in st.items() if isinstance(v, torch.Tensor)}
-                for p, st in self.optimizer.state.items()}
-
-    def _restore_optimizer(self, saved):
-        """Undo a warm-up's optimizer steps: state that existed before it gets its values
-        back, state the warm-up created (a fresh optimizer) is zeroed (step 0, zero moments)."""
-        with torch.no_grad():
-            for p, st in self.optimizer.state.items():
-                old = saved.get(id(p), {})
-                for k, v in st.items():
-                    if isinstance(v, torch.Tensor):
-                        if k in old:
-                            v.copy_(old[k])
-                        else:
-                            v.zero_()
-
-    def _allreduce(self):
-        if self._multi and self.train_graph:
-            lbdist.all_reduce_sum(self._gflat)
 
     def train_step(self, global_step):
         if self.train_graph:
             if self._tgraphs is None:
-                self._capture_train()
+                # the train step captured on the fixed sample buffers; its warm-up steps are
+                # undone and draw nothing from the sampling generator, so a graphed run trains
+                # exactly as an eager one
+                self._alloc_tstatic()
+                self._tgraphs, self._tloss = self._ts.capture(lambda: self._train_backward(*self._tstatic))
+                fused.invalidate(self.q_network)
             self.rb.sample_into(self.batch_size, self._tstatic)
-            self._tgraphs[0].replay()
-            if len(self._tgraphs) > 1:
-                self._allreduce()  # eager collective on the current stream, between the two graphs
-                self._tgraphs[1].replay()
+            self._ts.replay(self._tgraphs)
             loss = self._tloss
         else:
             loss = self._train_backward(*self.rb.sample(self.batch_size))
-            allreduce_gradients(self.q_network)
-            self._train_apply()
-        # the fused forward's cached weight image of the q network is stale now: neither a
-        # replayed Adam step nor torch's fused Adam kernel moves the version counters it keys on
-        fused.invalidate(self.q_network)
-        self.train_steps += 1
-        if global_step % self.target_network_frequency == 0:
-            # (dqn_deepset.py:199-203) in place on the parameters themselves, so their version
-            # counters move and the fused forward's cached weight image of the target is rebuilt
-            # (writes through .data would leave that image stale)
-            with torch.no_grad():
-                for tp, qp in zip(self.target_network.parameters(), self.q_network.parameters()):
-                    tp.copy_(self.tau * qp + (1.0 - self.tau) * tp)
-            fused.invalidate(self.target_network)
+            self._ts.allreduce()
+            self._ts.apply()
+        self._after_train(global_step, False)
         return loss
 
     def learn(self, total_timesteps: int = 500000):

@@ -18,8 +18,9 @@ GPU waiting on the host between the fused kernels.  With several ranks the step 
 graphs — loss/backward ending in the gradients packed into one flat bucket, then
 unpack/average + clip + Adam — with the bucket's all_reduce issued between them on the
 same stream (the collective stays outside the captures, so any backend works).  The
-capture's warm-up steps are undone (parameters restored, Adam state zeroed), so the graph
-path computes the same update as the eager one.
+capture's warm-up steps are undone (parameters and Adam state restored), so the graph path
+computes the same update as the eager one.  The step, its bucket and its capture are
+train_step.TrainStep, which DQN shares.
 
 With fused_act and fused_bookkeeping a rollout's vector step is three launches (lb_ds_sample,
 lb_step, lb_ppo_record) and GAE is one (lb_gae, gae_device); with fused_rollout the whole
@@ -35,8 +36,9 @@ from torch import nn, optim
 
 from . import _native
 from . import dist as lbdist
-from . import fused, fused_train
+from . import fused
 from .deepsets import DeepSetAgent
+from .train_step import TrainStep
 
 
 def ppo_loss(agent, obs, actions, logprobs_old, masks, advantages, returns, values_old,
@@ -183,9 +185,6 @@ class PPO_DeepSets:
         self._multi = lbdist.is_multi()
         if self._multi:
             lbdist.broadcast_parameters(self.agent)  # replicas start from rank 0's weights
-        # flat gradient bucket of the all_reduce (one collective per optimizer step)
-        self._gflat = torch.zeros(sum(p.numel() for p in self.agent.parameters()), device=self.device) \
-            if self._multi else None
         if use_graphs is None:
             use_graphs = self.device.type == "cuda"
         # a captured step needs equal minibatches and a device-side Adam step / lr
@@ -197,6 +196,8 @@ class PPO_DeepSets:
                                         fused=os.environ.get("LBK8S_FUSED_ADAM", "1") == "1")
         else:
             self.optimizer = optim.Adam(self.agent.parameters(), lr=learning_rate, eps=1e-5)
+        # backward -> [gradient all_reduce] -> clip_grad_norm -> Adam, eager or captured
+        self._ts = TrainStep(self.agent, self.optimizer, self.device, hook=self._clip)
         self._mb_graphs = None
         T, B = num_steps, self.num_envs
         R, A = env.observation_space.shape[0], env.action_space.n
@@ -291,89 +292,31 @@ class PPO_DeepSets:
         self._ep_cnt.zero_()
         return next_obs, next_done
 
-    def _mb_backward(self, obs, actions, logprobs, masks, adv, ret, val):
-        """Loss and gradients of one minibatch; with several ranks the gradients end packed
-        in the flat bucket that the all_reduce averages."""
-        out = ppo_loss(self.agent, obs, actions, logprobs, masks, adv, ret, val,
-                       self.clip_coef, self.ent_coef, self.vf_coef, self.norm_adv, self.clip_vloss)
-        # (also inside a captured step: autograd then allocates the gradients from the graph's
-        # pool, at the same addresses every replay, and no zero fill + accumulate per parameter
-        # is recorded)
-        self.optimizer.zero_grad(set_to_none=True)
-        # (a fixed unit seed: the fused loss head returns its saved gradients as they are)
-        seed = getattr(self, "_seed1", None)
-        if seed is None or seed.device != out[0].device or seed.dtype != out[0].dtype:
-            seed = self._seed1 = fused_train.unit_seed(out[0].device, out[0].dtype)
-        out[0].backward(seed)
-        if self._multi:
-            torch.cat([p.grad.reshape(-1) for p in self.agent.parameters()], out=self._gflat)
-        return out
-
-    def _mb_apply(self):
-        """Averaged gradients (several ranks) -> clip_grad_norm -> Adam."""
-        if self._multi:
-            self._gflat /= torch.distributed.get_world_size()
-            off = 0
-            for p in self.agent.parameters():
-                n = p.numel()
-                p.grad.copy_(self._gflat[off:off + n].view_as(p))
-                off += n
+    def _clip(self):
         nn.utils.clip_grad_norm_(self.agent.parameters(), self.max_grad_norm)
-        self.optimizer.step()
 
-    def _allreduce(self):
-        if self._multi:
-            lbdist.all_reduce_sum(self._gflat)
+    def _mb_backward(self, *mb):
+        """Loss and gradients of one minibatch (obs, actions, logprobs, masks, adv, ret, val)."""
+        out = ppo_loss(self.agent, *mb, self.clip_coef, self.ent_coef, self.vf_coef, self.norm_adv, self.clip_vloss)
+        self._ts.backward(out[0])
+        return out
 
     def _minibatch_step(self, *mb):
         out = self._mb_backward(*mb)
-        self._allreduce()
-        self._mb_apply()
+        self._ts.allreduce()
+        self._ts.apply()
         return out
 
     def _capture(self, src, mb):
-        """Capture one minibatch step on static buffers (filled from minibatch `mb`): one
-        graph on one rank, two graphs around the gradient all_reduce on several."""
+        """Capture one minibatch step on static buffers (filled from minibatch `mb`)."""
         self._static = [torch.empty((self.minibatch_size,) + t.shape[1:], dtype=t.dtype, device=t.device)
                         for t in src]
         for d, t in zip(self._static, src):
             torch.index_select(t, 0, mb, out=d)
-        params = list(self.agent.parameters())
-        snap = [p.detach().clone() for p in params]
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up: allocates grads, Adam state, workspaces
-                self._minibatch_step(*self._static)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        if self._multi:
-            ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ga):
-                self._static_out = self._mb_backward(*self._static)
-            with torch.cuda.graph(gb):
-                self._mb_apply()
-            graphs = (ga, gb)
-        else:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._static_out = self._minibatch_step(*self._static)
-            graphs = (g,)
-        with torch.no_grad():  # undo the warm-up steps
-            for p, q in zip(params, snap):
-                p.copy_(q)
-            for st in self.optimizer.state.values():
-                for v in st.values():
-                    if isinstance(v, torch.Tensor):
-                        v.zero_()
-        self._mb_graphs = graphs
+        self._mb_graphs, self._static_out = self._ts.capture(lambda: self._mb_backward(*self._static))
 
     def _replay(self):
-        if len(self._mb_graphs) == 1:
-            self._mb_graphs[0].replay()
-            return
-        self._mb_graphs[0].replay()
-        self._allreduce()  # eager collective on the current stream, between the two graphs
-        self._mb_graphs[1].replay()
+        self._ts.replay(self._mb_graphs)
 
     def update(self, next_obs, next_done):
         with torch.no_grad():

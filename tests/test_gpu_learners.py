@@ -68,6 +68,28 @@ def test_dqn_graph_train_step_matches_eager():
         torch.testing.assert_close(b, a, rtol=1e-4, atol=2e-6)
 
 
+def test_dqn_host_loop_graph_train_step_matches_eager():
+    """The host loop (device_rng=False: the explore draws and the replay sample on the host):
+    train_step replaying its captured graph on the fixed sample buffers trains as the eager
+    train step does -- the warm-up steps of the capture are undone and draw nothing, so both
+    runs take the same decisions and samples."""
+    from lbk8s import LBVecEnv
+    from lbk8s.dqn import DQN_DeepSets
+    res = []
+    for graph in (False, True):
+        env = LBVecEnv(64, seed=4, as_tensors=True, episode_length=10)
+        algo = DQN_DeepSets(env, buffer_size=6400, batch_size=64, learning_starts=50, train_frequency=5,
+                            target_network_frequency=100, seed=1, device_rng=False, train_graph=graph)
+        assert algo.train_graph == graph and not algo.device_rng and not algo.period_graph
+        algo.learn(total_timesteps=300)
+        assert (algo._tgraphs is not None) == graph
+        res.append((algo.train_steps, [p.detach().clone() for p in algo.q_network.parameters()]))
+    (na, pa), (nb, pb) = res
+    assert na == nb == len([s for s in range(300) if s > 50 and s % 5 == 0])
+    for a, b in zip(pa, pb):
+        torch.testing.assert_close(b, a, rtol=1e-4, atol=2e-6)
+
+
 def test_dqn_multi_step_periods_match_single_steps():
     """At config 5's shape (4096 envs: the one-launch vector step) a train period's vector steps
     run as ONE lb_dqn_steps launch; the learner then follows exactly the trajectory of one
