@@ -1,6 +1,6 @@
 // lbk8s_common.h — shared device code of the vectorized LoadBalancerK8sEnv kernels:
 // constants, packed-state bit layouts, Philox RNG, the float64 IEEE helpers, and the
-// kernel parameter block.  Included by lbk8s.hip only.
+// kernel parameter block.  Included by every unit of the library.
 //
 // Reference: /root/reference/envs/loadbalancer_k8s_env.py (constants :17-79) and
 // envs/utils.py (endpoint thresholds :33-64, gini :132-143).

@@ -1370,6 +1370,6 @@ __device__ __forceinline__ void ds_pack_one(const lb_ds_weights& w, float* out, 
     const bool gamma = r == 1 || r == 3 || r == 5 || r == 7 || r == 9 || r == 11;
     out[i] = gamma ? -v : v;
 }
-__global__ void k_ds_pack(lb_ds_weights w, float* out) { ds_pack_one(w, out, blockIdx.x * blockDim.x + threadIdx.x); }
+// (k_ds_pack, the kernel around ds_pack_one, is lbk8s_ds.hip's: a non-template kernel belongs to one unit)
 
 }  // namespace lbk

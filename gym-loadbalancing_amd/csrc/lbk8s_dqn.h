@@ -10,7 +10,7 @@
 // config 5 (4096 envs) the step and replay kernels were ~5 us each of mostly launch ramp and
 // tail (profiles/r03_dqn_kernel_stats_setgrads.csv); here they follow the forward inside the
 // same waves.  Same functions, same order per env: bit for bit the three launches
-// (tests/test_gpu_dqn_step.py).  The launch takes P = 2 envs per wave iteration (lbk8s.hip:
+// (tests/test_gpu_dqn_step.py).  The launch takes P = 2 envs per wave iteration (lbk8s_steps.hip:
 // STEPS_P; one env per wave measured slower: profiles/r06_dqn_p1_ab.jsonl).  The per-group
 // skeleton it shares with k_ppo_steps and k_eval_steps is StepsGroup (lbk8s_steps.h).
 #pragma once

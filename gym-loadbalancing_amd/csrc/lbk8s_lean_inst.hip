@@ -1,6 +1,6 @@
 // lbk8s_lean_inst.hip — the k_rollout_lean(_split) instantiations of ONE on-device policy
 // (LB_LEAN_KIND = LB_POLICY_*, set by csrc/Makefile: four objects from this file).  The kernels
-// are lbk8s_lean.h's; lb_rollout (lbk8s.hip) launches them through launch_lean.
+// are lbk8s_lean.h's; lb_rollout (lbk8s_env.hip) launches them through launch_lean.
 #include "lbk8s_lean.h"
 #include "lbk8s_lean_launch.h"
 

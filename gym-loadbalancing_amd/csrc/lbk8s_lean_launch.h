@@ -2,7 +2,7 @@
 //
 // The lean kernels are compiled in their own units, one per on-device policy
 // (lbk8s_lean_inst.hip built with -DLB_LEAN_KIND=0..3): 16 instantiations of a large kernel
-// per policy, compiled in parallel instead of inside lbk8s.hip.  lbk8s.hip's lb_rollout calls
+// per policy, compiled in parallel with the other units.  lbk8s_env.hip's lb_rollout calls
 // launch_lean through the explicit instantiations declared here.
 #pragma once
 

@@ -13,7 +13,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "liblbk8s.so
 _PRODUCT_LIB = LIB_PATH
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 # csrc/Makefile's SRCS, in order: the library embeds the SHA-256 of their concatenation
-SOURCES = ("lbk8s.hip", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
+SOURCES = ("lbk8s_env_steps.hip", "lbk8s_env.hip", "lbk8s_ds.hip", "lbk8s_ds_train.hip", "lbk8s_steps.hip",
+           "lbk8s_learn.hip", "lbk8s_host.h", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
            "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_steps.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "lbk8s_eval.h",
            "../../include/lbk8s.h",
            "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_build.cpp")
@@ -94,6 +95,68 @@ class LBSetJobC(C.Structure):
     _fields_ = [("a", C.c_void_p), ("lda", C.c_int64), ("b", C.c_void_p), ("ldb", C.c_int64), ("M", C.c_int32),
                 ("N", C.c_int32), ("scale", C.c_float), ("out", C.c_void_p)]
 
+
+def _prototypes():
+    """include/lbk8s.h's prototypes, name -> (restype, argtypes): the one place a signature is
+    written (tests/test_native_abi.py compares it with the header, argument by argument)."""
+    vp, i64, i32, u64, f32, f64 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_float, C.c_double
+    cfgp, trp, wp, exp = C.POINTER(LBConfigC), C.POINTER(LBTraceC), C.POINTER(LBDSWeightsC), C.POINTER(LBDQNExploreC)
+    i32p = C.POINTER(i32)
+    # lb_dqn_step up to ep_cnt (lb_dqn_steps continues with steps and sync)
+    dqn_step = [vp, vp, i64, i32, vp, vp, cfgp, exp] + [vp] * 6 + [i64] + [vp] * 9
+    # lb_ppo_record's / lb_ppo_steps' / lb_eval_steps' tail: tag, log, cap, count, stream
+    log_tail = [i64, vp, i64, vp, vp]
+    ints = {
+        "lb_abi_version": [],
+        "lb_validate_config": [cfgp],
+        "lb_state_bytes": [cfgp, i64, C.POINTER(u64)],
+        "lb_init": [vp, cfgp, i64, trp, vp],
+        "lb_reset": [vp, cfgp, i64, vp, vp, trp, vp],
+        "lb_step": [vp, cfgp, i64] + [vp] * 6 + [trp, vp],
+        "lb_rollout": [vp, cfgp, i64, i32, i32] + [vp] * 7,
+        "lb_rollout_kernel": [cfgp, i64, i32, i32, i32p],
+        "lb_policy": [vp, cfgp, i64, i32, vp, vp],
+        "lb_get_field": [vp, cfgp, i64, i32, vp, vp],
+        "lb_get_stats": [vp, cfgp, i64, vp, vp],
+        "lb_status": [vp, cfgp, i64, vp, vp],
+        "lb_ds_pack": [wp, vp, vp],
+        "lb_ds_forward": [vp, vp, i64, i32, vp, vp, vp],
+        "lb_ds_q_argmax": [vp, vp, i64, i32] + [vp] * 4,
+        "lb_ds_sample": [vp, vp, i64, i32] + [vp] * 8,
+        "lb_replay_add": [i64, i32, i64] + [vp] * 16,
+        "lb_dqn_act": [vp, vp, i64, i32, vp, vp, cfgp, exp, vp, vp],
+        "lb_dqn_step": dqn_step + [vp],
+        "lb_dqn_steps_supported": [cfgp, i64, i32],
+        "lb_dqn_steps": dqn_step + [i32, vp, vp],
+        "lb_dqn_head": [vp] * 5 + [i64, i32, f32] + [vp] * 6,
+        "lb_replay_sample": [i64, i32, i64, i32, u64] + [vp] * 13,
+        "lb_reward64": [vp, cfgp, i64, C.POINTER(vp)],
+        "lb_episode_log": [i64] + [vp] * 7 + log_tail,
+        "lb_ppo_record": [i64] + [vp] * 10 + log_tail,
+        "lb_gae": [vp] * 5 + [i64, i64, f64, f64, vp, vp, vp],
+        "lb_ppo_steps_supported": [cfgp, i64, i32],
+        "lb_ppo_steps": [vp, vp, vp, cfgp, i64, i32, i32, i32] + [vp] * 16 + log_tail,
+        "lb_eval_steps_supported": [cfgp, i64, i32],
+        "lb_eval_steps": [vp, vp, vp, cfgp, i64, i32, vp, i32] + [vp] * 11 + log_tail,
+        "lb_ds_train_forward": [vp, vp, i64, i32] + [vp] * 6,
+        "lb_ds_forward_pair": [vp] * 8 + [i64, i32, vp],
+        "lb_ds_forward_kernel": [i32, i64, i32, i32p, i32p, i32p],
+        "lb_ppo_head": [vp] * 8 + [i64, i32, f32, f32, f32, i32, vp, vp, vp, vp],
+        "lb_ds_pack_backward": [wp, vp, vp],
+        "lb_ds_pack_pair": [wp, vp, vp, vp],
+        "lb_ds_train_backward": [vp, vp, i64, i32] + [vp] * 8,
+        "lb_ds_set_grads": [vp, vp, vp, i64, i32, vp, vp],
+        "lb_ds_train_backward_sets": [vp, vp, i64, i32] + [vp] * 9,
+        "lb_ds_over_sets": [C.POINTER(LBSetJobC), i32, i64, vp, i64, vp],
+    }
+    protos = {name: (C.c_int, args) for name, args in ints.items()}
+    for name in ("lb_last_error", "lb_source_hash", "lb_build_flags", "lb_build_compiler"):
+        protos[name] = (C.c_char_p, [])
+    return protos
+
+
+PROTOTYPES = _prototypes()
+EXPORTED_SYMBOLS = tuple(PROTOTYPES)
 
 _lib = None
 
@@ -192,69 +255,13 @@ def lib():
     product = os.path.abspath(LIB_PATH) == _PRODUCT_LIB
     if not product:  # a diagnostic build (tools/ A/B runs): an older ABI may lack symbols
         L = _Tolerant(L)
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
-    cfgp = C.POINTER(LBConfigC)
-    trp = C.POINTER(LBTraceC)
-    L.lb_abi_version.restype = C.c_int
-    L.lb_last_error.restype = C.c_char_p
-    L.lb_validate_config.argtypes = [cfgp]
-    L.lb_state_bytes.argtypes = [cfgp, i64, C.POINTER(C.c_uint64)]
-    L.lb_init.argtypes = [vp, cfgp, i64, trp, vp]
-    L.lb_reset.argtypes = [vp, cfgp, i64, vp, vp, trp, vp]
-    L.lb_step.argtypes = [vp, cfgp, i64, vp, vp, vp, vp, vp, vp, trp, vp]
-    L.lb_policy.argtypes = [vp, cfgp, i64, i32, vp, vp]
-    L.lb_rollout.argtypes = [vp, cfgp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.lb_rollout_kernel.argtypes = [cfgp, i64, i32, i32, C.POINTER(C.c_int32)]
-    L.lb_get_field.argtypes = [vp, cfgp, i64, i32, vp, vp]
-    L.lb_get_stats.argtypes = [vp, cfgp, i64, vp, vp]
-    L.lb_status.argtypes = [vp, cfgp, i64, vp, vp]
-    L.lb_ds_pack.argtypes = [C.POINTER(LBDSWeightsC), vp, vp]
-    L.lb_ds_forward.argtypes = [vp, vp, i64, i32, vp, vp, vp]
-    L.lb_ds_q_argmax.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
-    L.lb_ds_sample.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    f32 = C.c_float
-    L.lb_ppo_head.argtypes = [vp] * 8 + [i64, i32, f32, f32, f32, i32, vp, vp, vp, vp]
-    L.lb_replay_add.argtypes = [i64, i32, i64] + [vp] * 15 + [vp]
-    L.lb_ds_train_forward.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, vp]
-    L.lb_ds_pack_backward.argtypes = [C.POINTER(LBDSWeightsC), vp, vp]
-    L.lb_ds_forward_pair.argtypes = [vp] * 8 + [i64, i32, vp]
-    L.lb_ds_forward_kernel.argtypes = [i32, i64, i32] + [C.POINTER(C.c_int32)] * 3
-    L.lb_ds_pack_pair.argtypes = [C.POINTER(LBDSWeightsC), vp, vp, vp]
-    L.lb_ds_train_backward.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.lb_episode_log.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp]
-    L.lb_ppo_record.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp]
-    L.lb_gae.argtypes = [vp] * 5 + [i64, i64, C.c_double, C.c_double, vp, vp, vp]
-    L.lb_ppo_steps_supported.argtypes = [cfgp, i64, i32]
-    L.lb_ppo_steps.argtypes = [vp, vp, vp, cfgp, i64, i32, i32, i32] + [vp] * 16 + [i64, vp, i64, vp, vp]
-    L.lb_eval_steps_supported.argtypes = [cfgp, i64, i32]
-    L.lb_eval_steps.argtypes = [vp, vp, vp, cfgp, i64, i32, vp, i32] + [vp] * 11 + [i64, vp, i64, vp, vp]
-    L.lb_reward64.argtypes = [vp, cfgp, i64, C.POINTER(C.c_void_p)]
-    L.lb_dqn_act.argtypes = [vp, vp, i64, i32, vp, vp, cfgp, C.POINTER(LBDQNExploreC), vp, vp]
-    L.lb_dqn_step.argtypes = [vp, vp, i64, i32, vp, vp, cfgp, C.POINTER(LBDQNExploreC), vp, vp, vp, vp, vp, vp,
-                              i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.lb_dqn_steps.argtypes = L.lb_dqn_step.argtypes[:-1] + [i32, vp, vp]
-    L.lb_dqn_steps_supported.argtypes = [cfgp, i64, i32]
-    L.lb_dqn_head.argtypes = [vp, vp, vp, vp, vp, i64, i32, C.c_float, vp, vp, vp, vp, vp, vp]
-    L.lb_replay_sample.argtypes = [i64, i32, i64, i32, C.c_uint64] + [vp] * 12 + [vp]
-    L.lb_ds_set_grads.argtypes = [vp, vp, vp, i64, i32, vp, vp]
-    L.lb_ds_train_backward_sets.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.lb_ds_over_sets.argtypes = [C.POINTER(LBSetJobC), i32, i64, vp, i64, vp]
-    for f in ("lb_validate_config", "lb_state_bytes", "lb_init", "lb_reset", "lb_step", "lb_policy", "lb_rollout",
-              "lb_rollout_kernel", "lb_reward64",
-              "lb_get_field", "lb_get_stats", "lb_status", "lb_ds_pack", "lb_ds_forward",
-              "lb_ds_train_forward", "lb_ds_pack_backward", "lb_ds_train_backward", "lb_ds_q_argmax",
-              "lb_replay_add", "lb_ppo_head", "lb_episode_log", "lb_dqn_act", "lb_dqn_head",
-              "lb_replay_sample", "lb_ds_set_grads", "lb_dqn_step", "lb_dqn_steps",
-              "lb_dqn_steps_supported", "lb_ds_pack_pair", "lb_ds_forward_pair", "lb_ds_over_sets",
-              "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample", "lb_ppo_record", "lb_gae",
-              "lb_ppo_steps_supported", "lb_ppo_steps", "lb_eval_steps_supported", "lb_eval_steps"):
-        getattr(L, f).restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(L, name)  # (a diagnostic library's stand-in where it lacks the symbol)
+        f.restype, f.argtypes = restype, argtypes
     v = L.lb_abi_version()
     if v != ABI_VERSION and product:
         raise RuntimeError(f"liblbk8s.so ABI {v} != expected {ABI_VERSION}; rebuild it")
     if product:  # (another LIB_PATH: a diagnostic build of other sources, tools/ only)
-        for f in ("lb_source_hash", "lb_build_flags", "lb_build_compiler"):
-            getattr(L, f).restype = C.c_char_p
         built, now = L.lb_source_hash().decode(), source_hash()
         if now is not None and built != now:
             raise StaleNativeLibrary(f"{LIB_PATH} was built from sources {built}, the tree's are {now}: "
@@ -275,16 +282,3 @@ def check(rc):
     if msg.startswith("IndexError"):
         raise IndexError(msg)
     raise RuntimeError(f"liblbk8s: {msg} (rc={rc})")
-
-
-EXPORTED_SYMBOLS = ("lb_abi_version", "lb_last_error", "lb_validate_config", "lb_state_bytes",
-                    "lb_init", "lb_reset", "lb_step", "lb_policy", "lb_rollout", "lb_get_field", "lb_get_stats",
-                    "lb_status", "lb_ds_pack", "lb_ds_forward", "lb_ds_train_forward",
-                    "lb_ds_pack_backward", "lb_ds_train_backward", "lb_ds_q_argmax", "lb_replay_add", "lb_ppo_head",
-                    "lb_episode_log", "lb_dqn_act", "lb_dqn_head", "lb_replay_sample", "lb_ds_set_grads",
-                    "lb_rollout_kernel", "lb_source_hash", "lb_build_flags", "lb_build_compiler", "lb_reward64",
-                    "lb_dqn_step",
-                    "lb_dqn_steps", "lb_dqn_steps_supported", "lb_ds_pack_pair", "lb_ds_forward_pair",
-                    "lb_ds_over_sets", "lb_ds_train_backward_sets", "lb_ds_forward_kernel", "lb_ds_sample",
-                    "lb_ppo_record", "lb_gae", "lb_ppo_steps_supported", "lb_ppo_steps",
-                    "lb_eval_steps_supported", "lb_eval_steps")

@@ -38,7 +38,7 @@ def _orc_policy(orc, kind):
 
 KINDS = ["random", "topo", "zone_cpu", "endpoint_cpu"]
 # (B, cfg, K, L, launches).  K <= 32: the split layout (an env wave and a copy wave per block,
-# k_rollout_lean_split); longer launches: the single-wave layout (lbk8s.hip: LEAN_SPLIT_MAX_K)
+# k_rollout_lean_split); longer launches: the single-wave layout (lbk8s_lean_launch.h: LEAN_SPLIT_MAX_K)
 # L == K: every env ends once in every launch
 SHAPES_L_EQ_K = [(131072, c, 20, 20, 2) for c in CFGS] + [(65600, "default", 20, 20, 2), (65600, "cfg1_multi", 20, 20, 2),
                                                          (65600, "default", 40, 40, 2), (65600, "cfg1_multi", 40, 40, 2)]

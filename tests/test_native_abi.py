@@ -36,6 +36,123 @@ def test_library_exports_every_declared_symbol():
     assert L.lb_abi_version() == _native.ABI_VERSION
 
 
+def header_text():
+    """include/lbk8s.h without its comments."""
+    src = open(HEADER).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+
+
+# scalar C types of the ABI -> (kind, bytes); a ctypes scalar is described the same way
+C_SCALARS = {"int32_t": "i4", "int": "i4", "int64_t": "i8", "uint64_t": "u8", "float": "f4", "double": "f8"}
+
+
+def header_prototypes():
+    """{name: (return, [argument, ...])} of every lb_* prototype in the header, each entry "ptr"
+    or a C_SCALARS value (an unknown scalar type stays as its C spelling, which matches nothing)."""
+    def kind(decl, is_param):
+        decl = decl.strip()
+        if "*" in decl or "[" in decl:
+            return "ptr"
+        words = [w for w in decl.split() if w != "const"]
+        ctype = " ".join(words[:-1] if is_param and len(words) > 1 else words)
+        return C_SCALARS.get(ctype, ctype)
+
+    out = {}
+    for ret, name, args in re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(lb_\w+)\s*\(([^)]*)\)\s*;", header_text(), re.M):
+        args = args.strip()
+        out[name] = (kind(ret, False), [] if args in ("", "void") else [kind(a, True) for a in args.split(",")])
+    return out
+
+
+def ctype_kind(t):
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    code = {"f": "f", "d": "f"}.get(t._type_, "u" if t._type_.isupper() else "i")
+    return f"{code}{C.sizeof(t)}"
+
+
+def abi_mismatches(header, table):
+    """Where a ctypes table {name: (restype, argtypes)} and the header's prototypes disagree: a
+    missing name, the return type, the arity, or an argument (pointer against scalar, and for
+    scalars the exact type)."""
+    bad = [f"{n}: in one of header / table only" for n in sorted(set(header) ^ set(table))]
+    for n in sorted(set(header) & set(table)):
+        (hret, hargs), (restype, argtypes) = header[n], table[n]
+        if ctype_kind(restype) != hret:
+            bad.append(f"{n}: returns {hret} in the header, {ctype_kind(restype)} in the table")
+        if len(hargs) != len(argtypes):
+            bad.append(f"{n}: {len(hargs)} arguments in the header, {len(argtypes)} in the table")
+            continue
+        bad += [f"{n}: argument {i} is {h} in the header, {ctype_kind(t)} in the table"
+                for i, (h, t) in enumerate(zip(hargs, argtypes)) if ctype_kind(t) != h]
+    return bad
+
+
+def test_prototypes_match_header():
+    """_native.PROTOTYPES against include/lbk8s.h, argument by argument (no library needed): the
+    arity, pointer against scalar, and the exact scalar type."""
+    from lbk8s import _native
+    header = header_prototypes()
+    assert len(header) == 45 and set(header) == set(declared_functions())
+    assert header["lb_gae"][1] == ["ptr"] * 5 + ["i8", "i8", "f8", "f8", "ptr", "ptr", "ptr"]  # (the parser itself)
+    assert header["lb_replay_sample"][1][:5] == ["i8", "i4", "i8", "i4", "u8"]
+    assert header["lb_last_error"] == ("ptr", []) and header["lb_abi_version"] == ("i4", [])
+    assert abi_mismatches(header, _native.PROTOTYPES) == []
+
+
+def test_prototypes_comparer_reports_mismatches():
+    """The negative control of test_prototypes_match_header: an argument dropped and an int32_t
+    widened to int64_t are both reported."""
+    from lbk8s import _native
+    header = header_prototypes()
+    dropped = dict(_native.PROTOTYPES)
+    restype, args = dropped["lb_ppo_steps"]
+    dropped["lb_ppo_steps"] = (restype, args[:10] + args[11:])  # one of the sixteen pointers
+    assert abi_mismatches(header, dropped) == ["lb_ppo_steps: 29 arguments in the header, 28 in the table"]
+    widened = dict(_native.PROTOTYPES)
+    restype, args = widened["lb_rollout"]
+    assert args[3] is C.c_int32
+    widened["lb_rollout"] = (restype, args[:3] + [C.c_int64] + args[4:])
+    assert abi_mismatches(header, widened) == ["lb_rollout: argument 3 is i4 in the header, i8 in the table"]
+    missing = {n: p for n, p in _native.PROTOTYPES.items() if n != "lb_gae"}
+    assert abi_mismatches(header, missing) == ["lb_gae: in one of header / table only"]
+
+
+def header_constants():
+    """{name: value} of the header's integer #defines and enumerators.  Reads the header as it is
+    written today: every enumerator with `= value`, every #define a plain integer or a product
+    of earlier constants.  A `u` suffix, a cast or an enumerator without a value makes this
+    raise (the test then errors rather than reports); extend the parser with the header."""
+    text, out = header_text(), {}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", text, re.S):
+        for item in filter(None, (x.strip() for x in body.split(","))):
+            name, value = (x.strip() for x in item.split("="))  # (every enumerator of the ABI has its value)
+            out[name] = int(value, 0)
+    for name, value in re.findall(r"^#define\s+(LB\w+)[ \t]+(\S[^\n]*)$", text, re.M):
+        out[name] = int(eval(value, {"__builtins__": {}}, dict(out)))  # (products of earlier constants)
+    return out
+
+
+def test_constants_match_header():
+    """Every constant the binding restates has the header's value."""
+    from lbk8s import _native
+    h = header_constants()
+    assert h["LB_ST_K"] == 16 and h["LB_DS_WORKSPACE_FLOATS"] == 1024 * 2 * 4608 and h["LB_FIELD_COUNT"] == 12
+    shared = {n: v for n, v in vars(_native).items() if n.startswith("LB_") and type(v) is int and n in h}
+    assert len(shared) >= 28, sorted(shared)
+    assert {n: h[n] for n in shared} == shared
+    assert _native.ABI_VERSION == h["LBK8S_ABI_VERSION"]
+    assert _native.LB_DSV == {n[len("LB_DSV_"):]: v for n, v in h.items() if n.startswith("LB_DSV_")}
+
+    def enum(prefix, without=()):
+        return {v for n, v in h.items() if n.startswith(prefix) and n[len(prefix):] not in without}
+    assert set(_native.LB_REWARD.values()) == enum("LB_REWARD_")
+    assert set(_native.LB_POLICY.values()) == enum("LB_POLICY_")
+    assert set(_native.LB_FIELD.values()) == enum("LB_FIELD_", without=("DT", "COUNT"))  # (left out on purpose)
+    assert set(_native.LB_GEOMETRY.values()) == enum("LB_GEOMETRY_")
+    assert set(_native.LB_ROLLOUT) == enum("LB_ROLLOUT_")
+
+
 def test_struct_sizes_match_header_layout():
     from lbk8s import _native
     # 8 x int32 + 5 x double + uint64 + int64 + 2 x int32 = 32 + 40 + 16 + 8
@@ -49,7 +166,7 @@ def test_struct_offsets_match_compiled_header(tmp_path):
 
     from lbk8s import _native
     structs = {"lb_config": _native.LBConfigC, "lb_trace": _native.LBTraceC, "lb_ds_weights": _native.LBDSWeightsC,
-               "lb_dqn_explore": _native.LBDQNExploreC}
+               "lb_dqn_explore": _native.LBDQNExploreC, "lb_set_job": _native.LBSetJobC}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "lbk8s.h"', "int main(void) {"]
     for cname, cls in structs.items():
         lines.append(f'printf("{cname} sizeof %zu\\n", sizeof({cname}));')
