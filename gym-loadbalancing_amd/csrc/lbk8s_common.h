@@ -289,6 +289,28 @@ __device__ __forceinline__ double accept_reward(const Params& p, double sel_lat,
     }
 }
 
+// The reward step(e) would return on the current state, for an endpoint e (the what-if of
+// LB_POLICY_REWARD_GREEDY): take_action's values for the selected endpoint -- its latency and
+// cpu before the increment, its topology latency to the request's zone, the Gini numerator
+// and the accept count after the accept -- handed to accept_reward, so the value is the
+// step's own, bit for bit.  cnt = #{e' != e : j_e' <= j_e}, the caller's count over the env's
+// history counters (the O(E) Gini update of the step kernels).  The table values a reward
+// function does not read are not gathered.
+__device__ __forceinline__ double whatif_accept_reward(const Params& p, double lat0, uint32_t em, uint32_t ed,
+                                                       int cnt, uint64_t topo, int rz, uint64_t acc2, int acc) {
+    const int rf = p.reward_fn;
+    const double sel_lat = (rf == LB_REWARD_LATENCY || rf == LB_REWARD_MULTI) ? lat_of(p, lat0, ed) : 0.0;
+    const double sel_cpu = rf == LB_REWARD_MULTI ? cpu_of(p, em, ed) : 0.0;
+    const int tl = topo_val(topo, rz, em_zone(em));
+    const uint32_t gnum = (uint32_t)(acc2 >> 32) + (uint32_t)(2 * (2 * cnt - (p.E - 1)));
+    const uint64_t acc2n = ((uint64_t)gnum << 32) | (uint32_t)((uint32_t)acc2 + (uint32_t)tl);
+    return accept_reward(p, sel_lat, tl, sel_cpu, acc2n, acc < 0xFFFF ? acc + 1 : 0xFFFF);
+}
+// ... and for the reject action (the step kernels' constant)
+__device__ __forceinline__ double whatif_reject_reward(const Params& p) {
+    return p.reward_fn == LB_REWARD_LATENCY ? -1000.0 : -1.0;
+}
+
 // ---- exact episode sums -------------------------------------------------------------
 // The reference's per-episode means are statistics.mean over lists of float64 values
 // (loadbalancer_k8s_env.py:451-454, :491-506): an exact rational sum, correctly rounded

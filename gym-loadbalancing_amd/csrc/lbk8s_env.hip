@@ -17,7 +17,9 @@
 // Compiled together with lbk8s_steps.hip (the one-launch step kernels) as lbk8s_env_steps.hip.
 // The library's other units: lbk8s_ds.hip (deep-sets forwards), lbk8s_ds_train.hip (their
 // training side), lbk8s_learn.hip (replay, episode log, GAE), lbk8s_lean_inst.hip (the lean
-// rollout, one unit per policy).
+// rollout, one unit per policy).  lbk8s_policies.hip (the policies LB_POLICY_ROUND_ROBIN ..
+// LB_POLICY_REWARD_GREEDY: the reward-greedy lb_policy kernels and their lb_rollout kernels) is
+// compiled with lbk8s_learn.hip.
 
 #include <hip/hip_runtime.h>
 
@@ -100,6 +102,8 @@ __global__ void k_init(Params p, int trace) {
 // envs/baselines.py (:6-35): argmin topology latency / argmax zone cpu capacity / argmin
 // endpoint cpu over feasible = mask[:-1] (masks are all True, :808-821), first index on
 // ties (numpy); or a uniform random action keyed by (env, episode, step).  One lane/env.
+// Also round robin, least loaded and least latency (LB_POLICY_* 4..6, include/lbk8s.h), over all
+// E endpoints; reward greedy has kernels of its own (lbk8s_policies.hip).
 __global__ void k_policy(Params p, int kind, int32_t* out) {
     int64_t env = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (env >= p.B) return;
@@ -108,7 +112,12 @@ __global__ void k_policy(Params p, int kind, int32_t* out) {
         out[env] = random_action(p, env, p.acc3[env], s.step);
         return;
     }
-    const int nf = p.A - 1;
+    if (kind == LB_POLICY_ROUND_ROBIN) {
+        out[env] = s.step % p.E;
+        return;
+    }
+    // the baselines.py kinds: e < A - 1; the others (least loaded, least latency): every endpoint
+    const int nf = kind > LB_POLICY_RANDOM ? p.E : p.A - 1;
     if (nf <= 0) { out[env] = p.A - 1; return; }
     const uint64_t topo = p.topo[env], zc = p.zcap[env];
     double best = 0.0;
@@ -119,6 +128,9 @@ __global__ void k_policy(Params p, int kind, int32_t* out) {
         double val;
         if (kind == LB_POLICY_TOPOLOGY_GREEDY) val = (double)topo_val(topo, em_zone(em), s.rz);
         else if (kind == LB_POLICY_ZONE_CPU_GREEDY) val = -(double)zcap_val(zc, em_zone(em));
+        else if (kind == LB_POLICY_LEAST_LOADED) val = (double)ed_j(p.edyn[i]);
+        else if (kind == LB_POLICY_LEAST_LATENCY)
+            val = lat_of(p, p.lat0[i], p.edyn[i]) + (double)topo_val(topo, em_zone(em), s.rz);
         else val = cpu_of(p, em, p.edyn[i]);
         if (e == 0 || val < best) { best = val; bi = e; }
     }
@@ -345,19 +357,6 @@ int check_launch() {
     return 0;
 }
 
-#define LB_DISPATCH_SLICE(W_, EPL_, BODY)                                         \
-    do {                                                                          \
-        if (W_ == 16 && EPL_ == 1) { constexpr int W = 16, EPL = 1; BODY; }       \
-        else if (W_ == 16 && EPL_ == 2) { constexpr int W = 16, EPL = 2; BODY; }  \
-        else if (W_ == 16 && EPL_ == 4) { constexpr int W = 16, EPL = 4; BODY; }  \
-        else if (W_ == 32 && EPL_ == 4) { constexpr int W = 32, EPL = 4; BODY; }  \
-        else if (W_ == 32 && EPL_ == 1) { constexpr int W = 32, EPL = 1; BODY; }  \
-        else if (W_ == 64 && EPL_ == 1) { constexpr int W = 64, EPL = 1; BODY; }  \
-        else if (W_ == 64 && EPL_ == 2) { constexpr int W = 64, EPL = 2; BODY; }  \
-        else if (W_ == 64 && EPL_ == 4) { constexpr int W = 64, EPL = 4; BODY; }  \
-        else return fail("unsupported geometry");                                 \
-    } while (0)
-
 unsigned slice_blocks(int64_t B, int W) {
     int64_t per = BLOCK / W;
     return (unsigned)((B + per - 1) / per);
@@ -566,8 +565,9 @@ int lb_rollout(void* state, const lb_config* cfg, int64_t num_envs, int32_t poli
     if (int r = validate(cfg)) return r;
     if (!state || num_envs < 1) return fail("state NULL or num_envs < 1");
     if (cfg->rng_mode != LB_RNG_PHILOX) return fail("lb_rollout draws in Philox mode only");
-    if (policy < 0 || policy > LB_POLICY_RANDOM) return fail("unknown policy kind");
+    if (policy < 0 || policy > LB_POLICY_REWARD_GREEDY) return fail("unknown policy kind");
     if (steps < 0) return fail("steps must be >= 0");
+    const bool k8s = policy > LB_POLICY_RANDOM;  // kinds 4..7: kernels of lbk8s_policies.hip
     Geo g = geometry(cfg, num_envs);
     hipStream_t s = (hipStream_t)stream;
     if (g.tpe && g.NZW <= 2) {  // thread-per-env layout, N <= 64: K steps in one launch
@@ -582,6 +582,8 @@ int lb_rollout(void* state, const lb_config* cfg, int64_t num_envs, int32_t poli
         // episodes at least as long as the launch (an env ends at most once in it): next
         // episodes drawn before the first step
         const bool pre = cfg->auto_reset && cfg->episode_length >= steps;
+        // (no lean / image kernels for them: k_rollout_tpe at every shape)
+        if (k8s) return launch_rollout_k8s(p, g, policy, (int)steps, pre, actions_out, s);
         const int rk = rollout_kernel(cfg, num_envs, steps, obs_out && reward_out && done_out && terminal_obs_out &&
                                                                 ep_stats_out);
         if (rk == LB_ROLLOUT_LEAN || rk == LB_ROLLOUT_LEAN_SPLIT) {  // k_rollout_lean(_split) (lbk8s_lean.h), B % 64 == 0
@@ -634,6 +636,7 @@ int lb_rollout(void* state, const lb_config* cfg, int64_t num_envs, int32_t poli
     p.done = done_out;
     p.term_obs = terminal_obs_out;
     p.ep_stats = ep_stats_out;
+    if (k8s) return launch_rollout_k8s(p, g, policy, (int)steps, false, actions_out, s);
     if (g.W == 16 && g.EPL == 4 && p.E == 64 && p.R == 65 && g.NZW == 1) {  // config 4's shape, compile-time
         const dim3 grid(slice_blocks(num_envs, 16));
 #define LB_SL64(RF_) hipLaunchKernelGGL((k_rollout_slice<16, 4, 64, 65, 1, RF_>), grid, dim3(BLOCK), 0, s, p, \
@@ -658,8 +661,10 @@ int lb_policy(const void* state, const lb_config* cfg, int64_t num_envs, int32_t
               int32_t* actions_out, void* stream) {
     if (int r = validate(cfg)) return r;
     if (!state || !actions_out || num_envs < 1) return fail("state/actions_out NULL");
-    if (kind < 0 || kind > LB_POLICY_RANDOM) return fail("unknown policy kind");
+    if (kind < 0 || kind > LB_POLICY_REWARD_GREEDY) return fail("unknown policy kind");
     Params p = make_params(const_cast<void*>(state), cfg, num_envs);
+    if (kind == LB_POLICY_REWARD_GREEDY)
+        return launch_policy_reward_greedy(p, geometry(cfg, num_envs), actions_out, (hipStream_t)stream);
     hipLaunchKernelGGL(k_policy, dim3(env_blocks(num_envs)), dim3(BLOCK), 0, (hipStream_t)stream, p, (int)kind,
                        actions_out);
     return check_launch();

@@ -44,9 +44,32 @@ struct Offsets {
 Offsets offsets(const lb_config* c, int64_t B);
 Params make_params(void* state, const lb_config* c, int64_t B);
 
+// BODY with the slice geometry (Geo::W, Geo::EPL) as the constants W and EPL
+#define LB_DISPATCH_SLICE(W_, EPL_, BODY)                                         \
+    do {                                                                          \
+        if (W_ == 16 && EPL_ == 1) { constexpr int W = 16, EPL = 1; BODY; }       \
+        else if (W_ == 16 && EPL_ == 2) { constexpr int W = 16, EPL = 2; BODY; }  \
+        else if (W_ == 16 && EPL_ == 4) { constexpr int W = 16, EPL = 4; BODY; }  \
+        else if (W_ == 32 && EPL_ == 4) { constexpr int W = 32, EPL = 4; BODY; }  \
+        else if (W_ == 32 && EPL_ == 1) { constexpr int W = 32, EPL = 1; BODY; }  \
+        else if (W_ == 64 && EPL_ == 1) { constexpr int W = 64, EPL = 1; BODY; }  \
+        else if (W_ == 64 && EPL_ == 2) { constexpr int W = 64, EPL = 2; BODY; }  \
+        else if (W_ == 64 && EPL_ == 4) { constexpr int W = 64, EPL = 4; BODY; }  \
+        else return fail("unsupported geometry");                                 \
+    } while (0)
+
 unsigned slice_blocks(int64_t B, int W);
 unsigned env_blocks(int64_t B);
 int device_cus();
+
+// lbk8s_policies.hip: the launches of LB_POLICY_ROUND_ROBIN .. LB_POLICY_REWARD_GREEDY that have
+// kernels of their own (p, g: make_params / geometry of the call)
+//   lb_policy(LB_POLICY_REWARD_GREEDY): lanes over the endpoints in the slice layout with
+//   E > 8, else one lane per env
+int launch_policy_reward_greedy(const Params& p, const Geo& g, int32_t* actions_out, hipStream_t s);
+//   lb_rollout: k_rollout_slice_k8s (slice layout) / k_rollout_tpe<NB, KIND, PRE> (thread-per-env, N <= 64)
+int launch_rollout_k8s(const Params& p, const Geo& g, int policy, int steps, bool pre, int32_t* actions_out,
+                       hipStream_t s);
 
 // k_deepsets_fwd numbers its waves wave-major (wave w of block b = w * grid + b): every CU
 // gets a block as soon as there are as many groups as CUs (lbk8s_ds.hip)

@@ -311,3 +311,7 @@ int lb_gae(const float* rewards, const float* values, const float* dones, const 
 }
 
 }  // extern "C"
+
+// The kernels of the policies LB_POLICY_ROUND_ROBIN .. LB_POLICY_REWARD_GREEDY are compiled with this
+// unit (csrc/Makefile says why here).
+#include "lbk8s_policies.hip"

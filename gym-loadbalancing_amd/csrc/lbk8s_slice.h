@@ -547,6 +547,55 @@ __device__ __forceinline__ int slice_policy(const Params& p, int64_t env, int la
     return bi;
 }
 
+// LB_POLICY_ROUND_ROBIN .. LB_POLICY_REWARD_GREEDY (include/lbk8s.h) on the slice's registers:
+// all E endpoints (no mask[:-1]), first index on ties.  Same values as lb_policy.
+// Reward greedy: every lane takes the what-if reward of its own endpoint(s)
+// (whatif_accept_reward); the count cnt_e = #{e' != e : j_e' <= j_e} its Gini numerator needs
+// comes from the other lanes' history counters by shuffles, O(E) per lane.  The argmax is the
+// (value, index) minimum of the negated rewards (negation is exact and keeps ties).
+template <int W, int EPL>
+__device__ __forceinline__ int slice_policy_k8s(const Params& p, int lane, const SEnv<EPL>& v, int kind) {
+    const int E = p.E;
+    if (kind == LB_POLICY_ROUND_ROBIN) return v.s.step % E;
+    int cnt[EPL];
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) cnt[k] = 0;
+    if (kind == LB_POLICY_REWARD_GREEDY && (p.reward_fn == LB_REWARD_FAIRNESS || p.reward_fn == LB_REWARD_MULTI)) {
+#pragma unroll
+        for (int k2 = 0; k2 < EPL; ++k2) {
+            for (int l2 = 0; l2 < W && l2 + k2 * W < E; ++l2) {  // uniform over the wave
+                const int e2 = l2 + k2 * W, j2 = ed_j(shfl_u32<W>(v.ed[k2], l2));
+#pragma unroll
+                for (int k = 0; k < EPL; ++k)
+                    if (e2 != lane + k * W && j2 <= ed_j(v.ed[k])) ++cnt[k];
+            }
+        }
+    }
+    double best = 0.0;
+    int bi = 1 << 30;
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+        const int e = lane + k * W;
+        if (e >= E) continue;
+        double val;
+        if (kind == LB_POLICY_LEAST_LOADED) val = (double)ed_j(v.ed[k]);
+        else if (kind == LB_POLICY_LEAST_LATENCY)
+            val = lat_of(p, v.lat0[k], v.ed[k]) + (double)topo_val(v.topo, em_zone(v.em[k]), v.s.rz);
+        else val = -whatif_accept_reward(p, v.lat0[k], v.em[k], v.ed[k], cnt[k], v.topo, v.s.rz, v.acc2, v.s.acc);
+        if (bi == (1 << 30) || val < best) { best = val; bi = e; }
+    }
+#pragma unroll
+    for (int m = W / 2; m >= 1; m >>= 1) {  // (value, index) minimum over the slice, lower index on ties
+        const double ob = __shfl_xor(best, m, W);
+        const int oi = __shfl_xor(bi, m, W);
+        const bool take = oi != (1 << 30) && (bi == (1 << 30) || ob < best || (ob == best && oi < bi));
+        best = take ? ob : best;
+        bi = take ? oi : bi;
+    }
+    if (kind == LB_POLICY_REWARD_GREEDY && p.A > E && -whatif_reject_reward(p) < best) bi = E;
+    return bi;
+}
+
 // lb_rollout: K steps per launch under an on-device policy, the env state held in
 // registers between steps; step k's obs / reward / done go to slot k of the caller's
 // buffers.  Bit for bit K x (lb_policy + lb_step) (tests/test_gpu_api.py).
@@ -578,6 +627,49 @@ __global__ __launch_bounds__(BLOCK) void k_rollout_slice(Params pa, int kind, in
         const int ak = a;
         if (k + 1 < K) {  // step k + 1's gathers, issued before step k's stores
             a = slice_policy<W, EPL>(p, env, lane, v, kind);
+            pr = slice_prep<W, EPL>(p, v, a);
+        }
+        if (lane == 0) {
+            if (act_out) act_out[k * p.B + env] = ak;
+            if (p.reward) p.reward[k * p.B + env] = (float)reward;
+            if (p.done) p.done[k * p.B + env] = (uint8_t)done;
+        }
+        if (p.obs) slice_obs<W, EPL>(p, env, lane, v, p.obs + k * obs_slot);
+    }
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+        const int e = lane + k * W;
+        if (e < p.E) p.edyn[eidx(p, env, e)] = v.ed[k];
+    }
+    if (lane == 0) slice_store_scalars<EPL>(p, env, v);
+}
+
+// k_rollout_slice under LB_POLICY_ROUND_ROBIN .. LB_POLICY_REWARD_GREEDY (slice_policy_k8s): the
+// same loop, instantiated in lbk8s_policies.hip only.  The kind is a runtime argument of both,
+// so a kernel of their own keeps the new kinds' code out of the kernels that serve kinds 0..3.
+// The loop is written out a second time on purpose: with one body behind a policy flag, called
+// by both kernels, k_rollout_slice (and, with the body taking Params by reference, k_step_slice
+// and k_reset_slice too) compiled to other code than before.
+template <int W, int EPL>
+__global__ __launch_bounds__(BLOCK) void k_rollout_slice_k8s(Params pa, int kind, int K, int32_t* act_out) {
+    Params p = pa;
+    const int lane = threadIdx.x % W;
+    const int64_t env = (int64_t)blockIdx.x * (BLOCK / W) + threadIdx.x / W;
+    if (env >= p.B) return;
+    SEnv<EPL> v;
+    slice_load<W, EPL>(p, env, lane, v);
+    // the observed values live in registers for the whole launch: a step changes only the
+    // selected endpoint's (slice_apply), a reset sets them all (slice_reset)
+    slice_observe<EPL>(p, v);
+    const int64_t obs_slot = p.B * (int64_t)p.R * 8;
+    int a = slice_policy_k8s<W, EPL>(p, lane, v, kind);
+    SPrep pr = slice_prep<W, EPL>(p, v, a);
+    for (int k = 0; k < K; ++k) {
+        bool done;
+        const double reward = slice_apply<W, EPL, false, false>(p, env, lane, v, pr, done);
+        const int ak = a;
+        if (k + 1 < K) {  // step k + 1's gathers, issued before step k's stores
+            a = slice_policy_k8s<W, EPL>(p, lane, v, kind);
             pr = slice_prep<W, EPL>(p, v, a);
         }
         if (lane == 0) {

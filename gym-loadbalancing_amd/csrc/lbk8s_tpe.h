@@ -656,6 +656,49 @@ __device__ __forceinline__ int tpe_policy(const Params& p, int64_t ev, const TEn
     }
     return bi;
 }
+// ... and with the endpoints' initial latencies at hand (k_rollout_tpe, the one-lane-per-env
+// lb_policy kernel), every kind: LB_POLICY_ROUND_ROBIN .. LB_POLICY_REWARD_GREEDY
+// (include/lbk8s.h) read the float64 endpoint latency, which the kinds above do not.  They
+// look at all E endpoints (no mask[:-1]), lowest index on ties; kinds 0..3 are the function
+// above.
+template <int KIND>
+__device__ __forceinline__ int tpe_policy(const Params& p, int64_t ev, const TEnv& v, const double (&lat0)[TPE_E],
+                                          const uint32_t (&em)[TPE_E], const uint32_t (&ed)[TPE_E]) {
+    if constexpr (KIND <= LB_POLICY_RANDOM) {
+        return tpe_policy<KIND>(p, ev, v, em, ed);
+    } else if constexpr (KIND == LB_POLICY_ROUND_ROBIN) {
+        return v.s.step % p.E;
+    } else if constexpr (KIND == LB_POLICY_REWARD_GREEDY) {
+        // argmax of the reward step(a) would return, the reject action included
+        double best = 0.0;
+        int bi = 0;
+#pragma unroll
+        for (int e = 0; e < TPE_E; ++e) {
+            if (e >= p.E) continue;
+            const int j = ed_j(ed[e]);
+            int cnt = 0;
+#pragma unroll
+            for (int e2 = 0; e2 < TPE_E; ++e2)
+                if (e2 < p.E && e2 != e && ed_j(ed[e2]) <= j) ++cnt;
+            const double val = whatif_accept_reward(p, lat0[e], em[e], ed[e], cnt, v.topo, v.s.rz, v.acc2, v.s.acc);
+            if (e == 0 || val > best) { best = val; bi = e; }
+        }
+        if (p.A > p.E && whatif_reject_reward(p) > best) bi = p.E;
+        return bi;
+    } else {
+        double best = 0.0;
+        int bi = 0;
+#pragma unroll
+        for (int e = 0; e < TPE_E; ++e) {
+            if (e >= p.E) continue;
+            double val;
+            if constexpr (KIND == LB_POLICY_LEAST_LOADED) val = (double)ed_j(ed[e]);
+            else val = lat_of(p, lat0[e], ed[e]) + (double)topo_val(v.topo, em_zone(em[e]), v.s.rz);
+            if (e == 0 || val < best) { best = val; bi = e; }
+        }
+        return bi;
+    }
+}
 
 // lb_rollout on the thread-per-env layout: K vector steps under an on-device policy in ONE
 // launch, each lane's env held in registers from the first step to the last (including the
@@ -857,11 +900,11 @@ __global__ __launch_bounds__(NB) void k_rollout_tpe(Params p, int K, int32_t* ac
     // (PRE only: the in-loop block-list resets hold too many registers for it)
     TPrep pr;
     if constexpr (PRE) {
-        pr = tpe_prep(p, lat0, em, ed, tpe_policy<KIND>(p, ev, v, em, ed));
+        pr = tpe_prep(p, lat0, em, ed, tpe_policy<KIND>(p, ev, v, lat0, em, ed));
         tpe_prep_request(p, ev, v, pr);
     }
     for (int k = 0; k < K; ++k) {
-        if constexpr (!PRE) pr = tpe_prep(p, lat0, em, ed, tpe_policy<KIND>(p, ev, v, em, ed));
+        if constexpr (!PRE) pr = tpe_prep(p, lat0, em, ed, tpe_policy<KIND>(p, ev, v, lat0, em, ed));
         if (act_out && live) act_out[k * p.B + env] = pr.a;
         v.s.step = v.s.step < 0xFFFF ? v.s.step + 1 : 0xFFFF;
         const bool done = live && v.s.step == p.L;  // (:472)
@@ -892,7 +935,7 @@ __global__ __launch_bounds__(NB) void k_rollout_tpe(Params p, int K, int32_t* ac
                 new_episode = true;
             }
             if (k + 1 < K) {
-                pr = tpe_prep(p, lat0, em, ed, tpe_policy<KIND>(p, ev, v, em, ed));
+                pr = tpe_prep(p, lat0, em, ed, tpe_policy<KIND>(p, ev, v, lat0, em, ed));
                 tpe_prep_request(p, ev, v, pr);
             }
             tpe_obs_rows(p, mine, v, em, olat, ocpu);

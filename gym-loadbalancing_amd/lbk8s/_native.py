@@ -17,12 +17,15 @@ SOURCES = ("lbk8s_env_steps.hip", "lbk8s_env.hip", "lbk8s_ds.hip", "lbk8s_ds_tra
            "lbk8s_learn.hip", "lbk8s_host.h", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
            "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_steps.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "lbk8s_eval.h",
            "../../include/lbk8s.h",
-           "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_build.cpp")
+           "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_policies.hip", "lbk8s_build.cpp")
 ABI_VERSION = 17
 
 LB_REWARD = {"naive": 0, "latency": 1, "fairness": 2, "multi": 3}
 LB_RNG_PHILOX, LB_RNG_TRACE = 0, 1
-LB_POLICY = {"topo": 0, "zone_cpu": 1, "endpoint_cpu": 2, "random": 3}
+LB_POLICY = {"topo": 0, "zone_cpu": 1, "endpoint_cpu": 2, "random": 3,
+             "round_robin": 4, "least_loaded": 5, "least_latency": 6, "reward_greedy": 7}
+# kinds without lean / image rollout kernels (lb_rollout runs k_rollout_tpe in their place)
+POLICIES_WITHOUT_LEAN_KERNELS = ("round_robin", "least_loaded", "least_latency", "reward_greedy")
 # lb_ds_forward_kernel's `which` (include/lbk8s.h LB_DS_FWD*)
 LB_DS_FWD, LB_DS_FWD_TRAIN, LB_DS_FWD_ARGMAX, LB_DS_FWD_PAIR, LB_DS_FWD_SAMPLE = 0, 1, 2, 3, 5
 # lb_rollout_kernel's answers (include/lbk8s.h LB_ROLLOUT_*)

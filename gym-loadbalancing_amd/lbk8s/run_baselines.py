@@ -30,11 +30,14 @@ CFG1 = dict(num_nodes=48, num_zones=12, num_endpoints=6, rejection_allowed=True,
             call_duration_r=1, episode_length=100, reward_function="naive", latency_weight=1.0, cpu_weight=0.0,
             gini_weight=0.0)
 POLICIES = ("topo", "zone_cpu", "endpoint_cpu")
+# every deterministic on-device policy: the reference's three, then round robin, least loaded,
+# least latency and the one-step reward optimum (include/lbk8s.h LB_POLICY_* 4..7)
+DEVICE_POLICIES = POLICIES + ("round_robin", "least_loaded", "least_latency", "reward_greedy")
 
 
 @torch.no_grad()
 def run_baselines(policy="topo", n_episodes=2000, device="cuda", seed=42, env_id_offset=0, **env_kwargs):
-    """n_episodes greedy episodes -> dict: "returns" (float64, the reference's return_),
+    """n_episodes episodes of one of DEVICE_POLICIES -> dict: "returns" (float64, the reference's return_),
     "rewards" (steps, episodes) float32, the 12 numeric info keys of each episode's last
     step, "wall_s" of the rollout launch, "env_steps_per_s", and the per-episode CSV rows the
     reference's env appends at every episode end (loadbalancer_k8s_env.py:488-510):
@@ -42,8 +45,8 @@ def run_baselines(policy="topo", n_episodes=2000, device="cuda", seed=42, env_id
     episode i of the batch numbered i + 1 as the reference's sequential episode_count.
     execution_time (the reference's per-episode wall clock) is the launch's wall time per
     episode here (unpinned)."""
-    if policy not in POLICIES:
-        raise ValueError(f"unrecognized policy {policy!r} (one of {POLICIES})")
+    if policy not in DEVICE_POLICIES:
+        raise ValueError(f"unrecognized policy {policy!r} (one of {DEVICE_POLICIES})")
     kw = dict(CFG1)
     kw.update(env_kwargs)
     # one episode per env, no auto-reset (the reference resets explicitly per episode); the
@@ -90,7 +93,7 @@ def write_csvs(res, file_results_name, directory="."):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="greedy baselines (run_baselines.py)")
-    ap.add_argument("--policy", default="topo", choices=POLICIES)
+    ap.add_argument("--policy", default="topo", choices=DEVICE_POLICIES)
     ap.add_argument("--n_episodes", type=int, default=2000)
     ap.add_argument("--num_endpoints", type=int, default=6)
     ap.add_argument("--seed", type=int, default=42)

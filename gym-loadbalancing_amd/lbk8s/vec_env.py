@@ -602,8 +602,9 @@ class LBVecEnv:
 
     def rollout(self, kind, steps, obs_out=None, reward_out=None, done_out=None, actions_out=None,
                 terminal_obs_out=None, ep_stats_out=None):
-        """`steps` vector steps under an on-device policy ("topo" / "zone_cpu" /
-        "endpoint_cpu" / "random") in one launch (lb_rollout): the same trajectory as
+        """`steps` vector steps under an on-device policy (_native.LB_POLICY: "topo" / "zone_cpu" /
+        "endpoint_cpu" / "random", or "round_robin" / "least_loaded" / "least_latency" /
+        "reward_greedy") in one launch (lb_rollout): the same trajectory as
         `steps` x (policy(kind), step_device(actions)).  Step k's outputs go to slot k of
         obs_out (K, B, R, 8), reward_out (K, B), done_out (K, B) uint8, actions_out (K, B)
         int32 (each None = not written)."""
@@ -617,16 +618,27 @@ class LBVecEnv:
             self._ptr(terminal_obs_out if terminal_obs_out is not None else self.terminal_obs),
             self._ptr(ep_stats_out if ep_stats_out is not None else self.ep_stats), self._stream()))
 
-    def rollout_kernel(self, steps, outputs_all=True):
+    def rollout_kernel(self, steps, outputs_all=True, kind=None):
         """The kernel lb_rollout launches for `steps` vector steps with every output given
-        (outputs_all) or not (lb_rollout_kernel; host only)."""
+        (outputs_all) or not (lb_rollout_kernel; host only).  lb_rollout_kernel answers for the
+        policies 0..3; with kind one of _native.POLICIES_WITHOUT_LEAN_KERNELS those answers become
+        k_rollout_tpe (lb_rollout's rule)."""
         k = C.c_int32(-1)
         _native.check(self._L.lb_rollout_kernel(C.byref(self._c), self.num_envs, int(steps), int(bool(outputs_all)),
                                                 C.byref(k)))
-        return _native.LB_ROLLOUT[k.value]
+        name = _native.LB_ROLLOUT[k.value]
+        lean = ("k_rollout_lean", "k_rollout_lean_split", "k_rollout_img")
+        if kind in _native.POLICIES_WITHOUT_LEAN_KERNELS and name in lean:
+            return "k_rollout_tpe"
+        return name
 
     def policy(self, kind, out=None):
-        """Batched envs/baselines.py greedy policy or uniform random -> (B,) int32 device tensor."""
+        """Batched on-device policy (_native.LB_POLICY) -> (B,) int32 device tensor: an
+        envs/baselines.py greedy policy ("topo", "zone_cpu", "endpoint_cpu"), uniform "random",
+        "round_robin" (current_step mod E), "least_loaded" (argmin avg_load_served),
+        "least_latency" (argmin endpoint_latency + endpoint_topology_latency) or "reward_greedy"
+        (argmax over every action of the reward step() would return; always 0 under the naive
+        reward).  The last four look at all E endpoints; lowest index on ties."""
         out = out if out is not None else self.torch.empty(self.num_envs, dtype=self.torch.int32,
                                                            device=self.device)
         _native.check(self._L.lb_policy(self._ptr(self.state), C.byref(self._c), self.num_envs,

@@ -35,12 +35,28 @@ extern "C" {
 enum { LB_REWARD_NAIVE = 0, LB_REWARD_LATENCY = 1, LB_REWARD_FAIRNESS = 2, LB_REWARD_MULTI = 3 };
 /* where random draws come from */
 enum { LB_RNG_PHILOX = 0, LB_RNG_TRACE = 1 };
-/* policies: the three greedy heuristics of envs/baselines.py:6-35, plus uniform random */
+/* policies: the three greedy heuristics of envs/baselines.py:6-35, plus uniform random (0..3),
+ * and the baselines a Kubernetes load balancer ships plus the one-step optimum (4..7).
+ * Kinds 4..7 are not the reference's: they look at all E endpoints and so do not inherit
+ * baselines.py's feasible = mask[:-1], which never picks the last endpoint when rejection is
+ * off; kinds 4..6 never reject.  Masks are all True; the lowest index wins every tie. */
 enum {
     LB_POLICY_TOPOLOGY_GREEDY = 0,     /* baselines.py:6-13  argmin endpoint_topology_latency   */
     LB_POLICY_ZONE_CPU_GREEDY = 1,     /* baselines.py:16-24 argmax endpoint_zone_cpu_capacity   */
     LB_POLICY_ENDPOINT_CPU_GREEDY = 2, /* baselines.py:27-35 argmin endpoint_cpu_usage_percentage */
-    LB_POLICY_RANDOM = 3               /* action_space.sample() equivalent, Philox-keyed         */
+    LB_POLICY_RANDOM = 3,              /* action_space.sample() equivalent, Philox-keyed         */
+    LB_POLICY_ROUND_ROBIN = 4,         /* IPVS rr: current_step mod E, current_step the env's step
+                                          counter before the step (LB_FIELD_CURRENT_STEP; 0 after
+                                          a reset, auto-reset included)                          */
+    LB_POLICY_LEAST_LOADED = 5,        /* IPVS lc: argmin over e in [0, E) of avg_load_served[e]
+                                          (LB_FIELD_LOAD_SERVED)                                 */
+    LB_POLICY_LEAST_LATENCY = 6,       /* argmin over e in [0, E) of endpoint_latency[e] +
+                                          (double)endpoint_topology_latency[e]: one float64 add,
+                                          the sum the latency and multi rewards pay for         */
+    LB_POLICY_REWARD_GREEDY = 7        /* myopic: argmax over a in [0, A) of the float64 reward
+                                          lb_step(a) would return on the current state, the reject
+                                          action included where it exists.  Under the naive reward
+                                          every accept pays 1.0, so the action is always 0.      */
 };
 /* lb_get_field ids: the env attributes the reference exposes (baselines.py:13,24,35 read 2,3,1) */
 enum {
@@ -177,8 +193,7 @@ int lb_step(void* state, const lb_config* cfg, int64_t num_envs, const int32_t* 
             float* obs_out, float* reward_out, uint8_t* done_out, float* terminal_obs_out,
             double* ep_stats_out, const lb_trace* trace, void* stream);
 
-/* K vector steps under an on-device policy (LB_POLICY_*: the three envs/baselines.py
- * greedy heuristics or the uniform random action), bit for bit K x (lb_policy + lb_step):
+/* K vector steps under an on-device policy (LB_POLICY_*), bit for bit K x (lb_policy + lb_step):
  * the run_baselines.py loop (:60-78) and BASELINE config 2's random policy without a launch
  * per vector step.  Step k writes obs_out + k*B*R*8, reward_out + k*B, done_out + k*B and
  * actions_out + k*B (each NULL = skip); with cfg.auto_reset, terminal_obs_out / ep_stats_out
@@ -187,7 +202,9 @@ int lb_step(void* state, const lb_config* cfg, int64_t num_envs, const int32_t* 
  * k_rollout_tpe; the latter draws the next episode of every env that ends inside the launch
  * before its first step, into a scratch record that is part of the state layout); the
  * thread-per-env layout with num_nodes > 64 issues K policy + step launches instead and
- * then needs actions_out for the greedy policies. */
+ * then needs actions_out for every policy but LB_POLICY_RANDOM.  Kinds 4..7 run k_rollout_tpe
+ * wherever lb_rollout_kernel answers LEAN, LEAN_SPLIT or IMG (those kernels are built for kinds
+ * 0..3 only).  Refused: policy < 0 or > LB_POLICY_REWARD_GREEDY ("unknown policy kind"). */
 int lb_rollout(void* state, const lb_config* cfg, int64_t num_envs, int32_t policy, int32_t steps,
                float* obs_out, float* reward_out, uint8_t* done_out, int32_t* actions_out,
                float* terminal_obs_out, double* ep_stats_out, void* stream);
@@ -203,13 +220,16 @@ int lb_rollout(void* state, const lb_config* cfg, int64_t num_envs, int32_t poli
  *   LB_ROLLOUT_LEAN_SPLIT  k_rollout_lean_split: LB_ROLLOUT_LEAN's shapes at K <= 32 steps (an env
  *                          wave and a copy wave per block; ABI 10)
  * The LEAN / IMG kernels address with 32-bit byte offsets from scalar bases; above 4 GiB of
- * state (or of ep_stats rows, or of one obs slot for LEAN) lb_rollout takes LB_ROLLOUT_TPE. */
+ * state (or of ep_stats rows, or of one obs slot for LEAN) lb_rollout takes LB_ROLLOUT_TPE.
+ * The answer holds for policies 0..3: for LB_POLICY_ROUND_ROBIN .. LB_POLICY_REWARD_GREEDY read
+ * LEAN, LEAN_SPLIT and IMG as LB_ROLLOUT_TPE (the other three answers are theirs too). */
 enum { LB_ROLLOUT_LEAN = 0, LB_ROLLOUT_IMG = 1, LB_ROLLOUT_TPE = 2, LB_ROLLOUT_STEPS = 3, LB_ROLLOUT_SLICE = 4,
        LB_ROLLOUT_LEAN_SPLIT = 5 };
 int lb_rollout_kernel(const lb_config* cfg, int64_t num_envs, int32_t steps, int32_t outputs_all,
                       int32_t* kernel_out);
 
-/* Batched envs/baselines.py policies (and uniform random) on the current state. */
+/* Batched policies (LB_POLICY_*) on the current state: actions_out [B] int32.
+ * Refused: kind < 0 or > LB_POLICY_REWARD_GREEDY ("unknown policy kind"). */
 int lb_policy(const void* state, const lb_config* cfg, int64_t num_envs, int32_t kind,
               int32_t* actions_out, void* stream);
 
