@@ -198,3 +198,7 @@ int lb_ds_set_grads(const float* setvec, const float* dlogits, const float* dmea
 }
 
 }  // extern "C"
+
+// the one-launch step kernels for envs of up to 64 endpoints and their entry points, compiled in
+// this unit (the build's shortest; the set of units stays as it was: csrc/Makefile)
+#include "lbk8s_steps64.hip"

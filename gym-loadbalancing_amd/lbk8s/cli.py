@@ -62,7 +62,12 @@ def build_parser():
                    help="--testing plays the episodes one after another on one env, as run_test_deepset.py")
     p.add_argument("--test-fused", action="store_true",
                    help="--testing plays its episodes in one launch (run_test(fused=True)) where the env's shape "
-                        "has it (E <= 16, R <= 16, fewer than 32,768 episodes); ignored with --test_sequential")
+                        "has it (E <= 16, R <= 16, fewer than 32,768 episodes; with --test-fused-e64 E <= 64, "
+                        "R <= 65); ignored with --test_sequential")
+    p.add_argument("--test-fused-e64", action="store_true",
+                   help="--testing plays its episodes in one launch through lb_eval_steps64 "
+                        "(run_test(fused=True, e64=True)): E <= 64, R <= 65, fewer than 32,768 episodes; ignored "
+                        "with --test_sequential")
     p.add_argument("--device", default="cuda")
     p.add_argument("--seed", default=0, type=int, help="Philox seed of the envs")
     p.add_argument("--nproc", default=1, type=int, help="GPUs (ranks) to train on, one process each")
@@ -74,7 +79,10 @@ def build_parser():
                    help="ppo_deepsets: the rollout step's bookkeeping and GAE as one launch each")
     p.add_argument("--fused-rollout", action="store_true",
                    help="ppo_deepsets: a rollout's vector steps as one launch where the env's shape has it "
-                        "(E <= 16, R <= 16, fewer than 32,768 envs)")
+                        "(E <= 16, R <= 16, fewer than 32,768 envs; with --fused-rollout-e64 E <= 64, R <= 65)")
+    p.add_argument("--fused-rollout-e64", action="store_true",
+                   help="ppo_deepsets: a rollout's vector steps as one launch through lb_ppo_steps64 "
+                        "(PPO_DeepSets(fused_rollout_e64=True)): E <= 64, R <= 65, fewer than 32,768 envs")
     return p
 
 
@@ -101,7 +109,7 @@ def get_model(alg, env, rank=0, **ppo_flags):
     learner seed is offset by its rank, so rollout uniforms, minibatch permutations, replay
     samples and exploration coins differ across GPUs (the parameters are broadcast from rank
     0, so the replicas still start identical).  ppo_flags: PPO_DeepSets' fused_act /
-    fused_bookkeeping / fused_rollout (all off by default)."""
+    fused_bookkeeping / fused_rollout / fused_rollout_e64 (all off by default)."""
     if alg == "ppo_deepsets":
         from .ppo import PPO_DeepSets
         return PPO_DeepSets(env, num_steps=100, n_minibatches=8, ent_coef=0.001, seed=2 + rank, **ppo_flags)
@@ -143,7 +151,8 @@ def main(argv=None):
                       num_envs=args.num_envs, device=dev if world > 1 else args.device, seed=args.seed,
                       env_id_offset=rank * args.num_envs, monitor_file=mon)
         flags = dict(fused_act=args.fused_act, fused_bookkeeping=args.fused_bookkeeping,
-                     fused_rollout=args.fused_rollout) if alg == "ppo_deepsets" else {}
+                     fused_rollout=args.fused_rollout,
+                     fused_rollout_e64=args.fused_rollout_e64) if alg == "ppo_deepsets" else {}
         model = get_model(alg, env, rank, **flags)
         if args.loading:  # resume training
             model.load(args.load_path)
@@ -168,7 +177,7 @@ def main(argv=None):
             res = run_sequential(agent, args.test_episodes, env)
         else:
             res = run_test(agent, n_episodes=args.test_episodes, seed=args.seed, device=args.device,
-                           fused=args.test_fused, **kw)
+                           fused=args.test_fused or args.test_fused_e64, e64=args.test_fused_e64, **kw)
         result["test_returns"] = [float(r) for r in res["r"]]
     print(json.dumps(result))
     return result

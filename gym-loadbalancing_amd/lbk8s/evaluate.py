@@ -13,7 +13,9 @@ Two forms:
   episode (episode_length steps).  Episode i is the scenario of global env id
   `env_id_offset + i` (Philox), so any single episode can be replayed alone.
   With fused=True (the CLI's --test-fused) the whole episode is one launch (lb_eval_steps: the
-  argmax inside the forward kernel, the env in registers) where the env's shape has it.
+  argmax inside the forward kernel, the env in registers) where the env's shape has it: at most
+  16 observation rows, or with e64=True (--test-fused-e64, lb_eval_steps64) at most 65 (E <= 64),
+  fewer than 32,768 envs either way.
 * run_sequential: the reference loop as written — ONE env, episodes one after another,
   DummyVecEnv's auto-reset on done followed by the loop's own reset() (so the auto-reset's
   scenario is drawn and discarded), VecMonitor's float32 episode return.  Pinned by
@@ -68,7 +70,7 @@ def eval_image(agent, device):
 
 @torch.no_grad()
 def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", monitor_path=None, fused=False,
-             return_trace=False, **env_kwargs):
+             return_trace=False, e64=False, **env_kwargs):
     """Play n_episodes greedy episodes in parallel -> dict of per-episode numpy arrays:
     "r" return, "l" length, the 12 numeric info keys of the final step, and "wall_s".
 
@@ -76,14 +78,16 @@ def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", mo
     the whole episode in one launch (LBVecEnv.eval_steps; ValueError where the shape has none);
     None, the launch where it is supported, else the loop.  The launch takes the argmax inside
     the forward kernel, the loop torch's argmax of the forward's scores: a float32 near-tie may
-    resolve differently.  return_trace: also "actions" / "rewards" / "dones" (L, n), every step's."""
+    resolve differently.  return_trace: also "actions" / "rewards" / "dones" (L, n), every step's.
+    e64: the one launch is LBVecEnv.eval_steps64 (up to 64 endpoints: eval_steps64_supported) in
+    place of eval_steps; fused=True / None then ask that query.  False: eval_steps in every case."""
     kw = dict(TEST_ENV)
     kw.update(env_kwargs)
     env = LBVecEnv(n_episodes, device=device, seed=seed, env_id_offset=env_id_offset, auto_reset=False,
                    as_tensors=True, **kw)
     L = env.cfg.episode_length
     if fused or fused is None:
-        why = _no_one_launch(agent, env)
+        why = _no_one_launch(agent, env, e64)
         if why and fused:
             raise ValueError(f"run_test(fused=True): {why}")
         fused = not why
@@ -99,7 +103,7 @@ def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", mo
         _, frag = eval_image(agent, env.device)
         # (every action is always valid: action_masks() is all True, so no mask is passed; eval_steps
         # plays an episode longer than LB_EVAL_STEPS_MAX in launches of that many steps)
-        env.eval_steps(frag, obs, L, None, *(trace or ()))
+        (env.eval_steps64 if e64 else env.eval_steps)(frag, obs, L, None, *(trace or ()))
     else:
         t0 = time.time()
         for i in range(L):
@@ -122,11 +126,17 @@ def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", mo
     return out
 
 
-def _no_one_launch(agent, env):
-    """Why run_test cannot play `env` with `agent` in one launch (None: it can)."""
+def _no_one_launch(agent, env, e64=False):
+    """Why run_test cannot play `env` with `agent` in one launch (None: it can); e64: the launch
+    is eval_steps64."""
     net = (agent.actor if isinstance(agent, DeepSetAgent) else agent.q_network).net
     if not fused._geometry_ok(net, env.obs):
         return f"the fused forward does not cover this agent on {tuple(env.obs.shape)} observations"
+    if e64:
+        if not env.eval_steps64_supported(env.obs.shape[1]):
+            return (f"no one-launch evaluation for {env.num_envs} envs of {env.cfg.num_endpoints} endpoints "
+                    "(eval_steps64_supported: at most 65 observation rows, fewer than 32,768 envs)")
+        return None
     if not env.eval_steps_supported(env.obs.shape[1]):
         return (f"no one-launch evaluation for {env.num_envs} envs of {env.cfg.num_endpoints} endpoints "
                 "(eval_steps_supported: at most 16 observation rows, fewer than 32,768 envs)")

@@ -25,7 +25,8 @@ train_step.TrainStep, which DQN shares.
 With fused_act and fused_bookkeeping a rollout's vector step is three launches (lb_ds_sample,
 lb_step, lb_ppo_record) and GAE is one (lb_gae, gae_device); with fused_rollout the whole
 rollout's vector steps are ONE launch (lb_ppo_steps, LBVecEnv.ppo_steps) where the env's shape has
-it (E <= 16 below 32,768 envs, R <= 16).  All three flags are off by default.
+it (E <= 16 below 32,768 envs, R <= 16), and with fused_rollout_e64 where lb_ppo_steps64 has it
+(E <= 64 below 32,768 envs, R <= 65, Philox mode: config 4).  All four flags are off by default.
 """
 import os
 import time
@@ -149,7 +150,8 @@ class PPO_DeepSets:
                  clip_vloss: bool = True, ent_coef: float = 0.01, vf_coef: float = 0.5,
                  max_grad_norm: float = 0.5, target_kl: Optional[float] = None, seed: int = 1,
                  device=None, log_fn=None, num_envs=None, tensorboard_log=None, use_graphs=None,
-                 fused_act: bool = False, fused_bookkeeping: bool = False, fused_rollout: bool = False):
+                 fused_act: bool = False, fused_bookkeeping: bool = False, fused_rollout: bool = False,
+                 fused_rollout_e64: bool = False):
         # fused_act: the rollout's policy step as ONE launch (fused.deepsets_sample) that writes the
         # env's action buffer and the step's storage rows (actions, logprobs, values) directly.  Off
         # by default: a draw on a CDF boundary can pick the neighbouring row (and u = 0 never picks
@@ -165,6 +167,9 @@ class PPO_DeepSets:
         # bit, whose buffers it implies.  Effective where the sampling forward covers the agent,
         # the env has the one-launch shape (ppo_steps_supported) and the device is HIP; elsewhere
         # the attribute reads False and the other two flags decide.  Off by default.
+        # fused_rollout_e64: fused_rollout through LBVecEnv.ppo_steps64, whose shapes reach 64
+        # endpoints (ppo_steps64_supported: R <= 65 below 32,768 envs, Philox mode); where it holds,
+        # fused_rollout reads True.  fused_rollout alone keeps its 16-lane meaning.  Off by default.
         # num_envs / tensorboard_log: accepted for signature compatibility with
         # ppo_deepset.py:53-75 (the env's num_envs is used; there is no tensorboard writer)
         self.env = env
@@ -224,6 +229,10 @@ class PPO_DeepSets:
         self.fused_bookkeeping = bool(fused_bookkeeping) and dev.type == "cuda" and hasattr(env, "record_ppo")
         self.fused_rollout = (bool(fused_rollout) and dev.type == "cuda" and hasattr(env, "ppo_steps")
                               and fused.sample_supported(self.agent, self.obs[0]) and env.ppo_steps_supported(R))
+        self.fused_rollout_e64 = (bool(fused_rollout_e64) and dev.type == "cuda" and hasattr(env, "ppo_steps64")
+                                  and fused.sample_supported(self.agent, self.obs[0])
+                                  and env.ppo_steps64_supported(R))
+        self.fused_rollout = self.fused_rollout or self.fused_rollout_e64
         if self.fused_rollout:  # (its buffers are fused_bookkeeping's; GAE in one launch too)
             self.fused_bookkeeping = True
         self.advantages = self.returns = None  # the last update()'s
@@ -241,9 +250,10 @@ class PPO_DeepSets:
         if self.fused_rollout:  # one launch (per monitor flush): every storage row, the sums, the log
             self.dones[0] = next_done
             agent = self.agent
-            env.ppo_steps(fused.packed(agent, agent.actor.net, agent.critic), self.obs[0], self._u, self.actions,
-                          self.logprobs, self.values, self.rewards, self.obs[1:], self.dones[1:], self._last_obs,
-                          self._next_done, self._act, self._done_u8, self._ep_sum, self._ep_cnt)
+            steps = env.ppo_steps64 if self.fused_rollout_e64 else env.ppo_steps
+            steps(fused.packed(agent, agent.actor.net, agent.critic), self.obs[0], self._u, self.actions,
+                  self.logprobs, self.values, self.rewards, self.obs[1:], self.dones[1:], self._last_obs,
+                  self._next_done, self._act, self._done_u8, self._ep_sum, self._ep_cnt)
             return self._next_done
         next_obs = self.obs[0]
         fb = self.fused_bookkeeping

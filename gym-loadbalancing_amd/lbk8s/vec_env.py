@@ -461,6 +461,20 @@ class LBVecEnv:
         R-row observations."""
         return bool(self._L.lb_ppo_steps_supported(C.byref(self._c), self.num_envs, R))
 
+    def ppo_steps64_supported(self, R):
+        """Whether lb_ppo_steps64 (ppo_steps for envs of up to 64 endpoints: R <= 65 below 32,768
+        envs, Philox mode) covers this env with R-row observations; true wherever
+        ppo_steps_supported is."""
+        return bool(self._L.lb_ppo_steps64_supported(C.byref(self._c), self.num_envs, R))
+
+    def ppo_steps64(self, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next, dones_next,
+                    last_obs, last_done, actions, dones, ep_sum, ep_cnt):
+        """lb_ppo_steps64: ppo_steps, argument for argument, on the shapes of ppo_steps64_supported
+        (config 4's E = 64, R = 65 among them); on a shape ppo_steps covers, the same kernel."""
+        return self._ppo_steps("ppo_steps64", self._L.lb_ppo_steps64, frag, obs, uniforms, actions_f32, logprobs,
+                               values, rewards, obs_next, dones_next, last_obs, last_done, actions, dones, ep_sum,
+                               ep_cnt)
+
     def ppo_steps(self, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next, dones_next,
                   last_obs, last_done, actions, dones, ep_sum, ep_cnt):
         """lb_ppo_steps: T = uniforms.shape[0] PPO vector steps -- each fused.deepsets_sample on the
@@ -473,20 +487,26 @@ class LBVecEnv:
         as record_ppo's.  A monitored env logs every step with its own host time and flushes at
         record_ppo's cadence: the request is split into launches that end where a flush is due
         (within that many steps an env finishes at most once, so the log cannot overflow)."""
+        return self._ppo_steps("ppo_steps", self._L.lb_ppo_steps, frag, obs, uniforms, actions_f32, logprobs, values,
+                               rewards, obs_next, dones_next, last_obs, last_done, actions, dones, ep_sum, ep_cnt)
+
+    def _ppo_steps(self, who, entry, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next,
+                   dones_next, last_obs, last_done, actions, dones, ep_sum, ep_cnt):
+        """ppo_steps / ppo_steps64 (who: the method's name, entry: its library function)."""
         t = self.torch
         if not self._reset_called and not t.cuda.is_current_stream_capturing():
             raise TypeError("step() called before reset()")
         B = self.num_envs
         if not isinstance(uniforms, t.Tensor) or uniforms.dim() != 2 or uniforms.shape[0] < 1:
-            raise ValueError("ppo_steps: uniforms must be a (T, B) tensor with T >= 1")
+            raise ValueError(f"{who}: uniforms must be a (T, B) tensor with T >= 1")
         if not isinstance(obs, t.Tensor) or obs.dim() != 3:
-            raise ValueError("ppo_steps: obs must be a (B, R, 8) tensor")
+            raise ValueError(f"{who}: obs must be a (B, R, 8) tensor")
         T, R = uniforms.shape[0], obs.shape[1]
         S = obs_next.shape[0] if isinstance(obs_next, t.Tensor) and obs_next.dim() == 4 else -1
         if S not in (T, T - 1):
-            raise ValueError(f"ppo_steps: obs_next must be a ({T} or {T - 1}, {B}, {R}, 8) tensor")
+            raise ValueError(f"{who}: obs_next must be a ({T} or {T - 1}, {B}, {R}, 8) tensor")
         last = S == T and last_obs is None and last_done is None  # (last_* optional: every row is stored)
-        self._check_tensors("ppo_steps", [
+        self._check_tensors(who, [
             ("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32, False), ("obs", obs, (B, R, 8), t.float32, False),
             ("uniforms", uniforms, (T, B), t.float32, False), ("actions_f32", actions_f32, (T, B), t.float32, False),
             ("logprobs", logprobs, (T, B), t.float32, False), ("values", values, (T, B), t.float32, False),
@@ -495,12 +515,12 @@ class LBVecEnv:
             ("dones", dones, (B,), t.uint8, False), ("ep_sum", ep_sum, (B,), t.float64, False),
             ("ep_cnt", ep_cnt, (B,), t.float64, False), ("last_obs", last_obs, (B, R, 8), t.float32, last),
             ("last_done", last_done, (B,), t.float32, last)])
-        if not self.ppo_steps_supported(R):
-            raise RuntimeError("ppo_steps: the env's shape has no one-launch rollout (ppo_steps_supported)")
+        if not getattr(self, who + "_supported")(R):
+            raise RuntimeError(f"{who}: the env's shape has no one-launch rollout ({who}_supported)")
         for i, n in self._launches(T, _native.LB_PPO_STEPS_MAX):
             s = min(n, S - i)  # rows of obs_next / dones_next this launch fills (n, or n - 1 at the end)
             src = obs if i == 0 else obs_next[i - 1]
-            _native.check(self._L.lb_ppo_steps(
+            _native.check(entry(
                 self._ptr(frag), self._ptr(src), self._ptr(self.state), C.byref(self._c), B, R, n, s,
                 self._ptr(uniforms[i]), self._ptr(actions_f32[i]), self._ptr(logprobs[i]), self._ptr(values[i]),
                 self._ptr(rewards[i]), self._ptr(obs_next[i]) if s else None,
@@ -513,6 +533,19 @@ class LBVecEnv:
         """Whether lb_eval_steps (a greedy evaluation's vector steps in one launch) covers this env
         with R-row observations."""
         return bool(self._L.lb_eval_steps_supported(C.byref(self._c), self.num_envs, R))
+
+    def eval_steps64_supported(self, R):
+        """Whether lb_eval_steps64 (eval_steps for envs of up to 64 endpoints: R <= 65 below 32,768
+        envs, Philox mode) covers this env with R-row observations; true wherever
+        eval_steps_supported is."""
+        return bool(self._L.lb_eval_steps64_supported(C.byref(self._c), self.num_envs, R))
+
+    def eval_steps64(self, frag, obs, steps, masks=None, actions_all=None, rewards_all=None, dones_all=None,
+                     ep_sum=None, ep_cnt=None):
+        """lb_eval_steps64: eval_steps, argument for argument, on the shapes of eval_steps64_supported
+        (E = 64 with the reject row among them); on a shape eval_steps covers, the same kernel."""
+        return self._eval_steps("eval_steps64", self._L.lb_eval_steps64, frag, obs, steps, masks, actions_all,
+                                rewards_all, dones_all, ep_sum, ep_cnt)
 
     def eval_steps(self, frag, obs, steps, masks=None, actions_all=None, rewards_all=None, dones_all=None,
                    ep_sum=None, ep_cnt=None):
@@ -527,28 +560,33 @@ class LBVecEnv:
         float64, both or neither, as record_ppo's.  A monitored env logs every step with its own
         host time and flushes at record_ppo's cadence: the request is split into launches that end
         where a flush is due.  Returns obs."""
+        return self._eval_steps("eval_steps", self._L.lb_eval_steps, frag, obs, steps, masks, actions_all,
+                                rewards_all, dones_all, ep_sum, ep_cnt)
+
+    def _eval_steps(self, who, entry, frag, obs, steps, masks, actions_all, rewards_all, dones_all, ep_sum, ep_cnt):
+        """eval_steps / eval_steps64 (who: the method's name, entry: its library function)."""
         t = self.torch
         if not self._reset_called and not t.cuda.is_current_stream_capturing():
             raise TypeError("step() called before reset()")
         B = self.num_envs
         T = int(steps)
         if T < 1:
-            raise ValueError("eval_steps: steps must be >= 1")
+            raise ValueError(f"{who}: steps must be >= 1")
         if not isinstance(obs, t.Tensor) or obs.dim() != 3:
-            raise ValueError("eval_steps: obs must be a (B, R, 8) tensor")
+            raise ValueError(f"{who}: obs must be a (B, R, 8) tensor")
         if (ep_sum is None) != (ep_cnt is None):
-            raise ValueError("eval_steps: ep_sum and ep_cnt go together")
+            raise ValueError(f"{who}: ep_sum and ep_cnt go together")
         R = obs.shape[1]
-        self._check_tensors("eval_steps", [
+        self._check_tensors(who, [
             ("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32, False), ("obs", obs, (B, R, 8), t.float32, False),
             ("masks", masks, (B, R), t.bool, True), ("actions_all", actions_all, (T, B), t.int32, True),
             ("rewards_all", rewards_all, (T, B), t.float32, True), ("dones_all", dones_all, (T, B), t.uint8, True),
             ("ep_sum", ep_sum, (B,), t.float64, True), ("ep_cnt", ep_cnt, (B,), t.float64, True)])
-        if not self.eval_steps_supported(R):
-            raise RuntimeError("eval_steps: the env's shape has no one-launch evaluation (eval_steps_supported)")
+        if not getattr(self, who + "_supported")(R):
+            raise RuntimeError(f"{who}: the env's shape has no one-launch evaluation ({who}_supported)")
         for i, n in self._launches(T, _native.LB_EVAL_STEPS_MAX):
             row = lambda x: self._ptr(x[i]) if x is not None else None
-            _native.check(self._L.lb_eval_steps(
+            _native.check(entry(
                 self._ptr(frag), self._ptr(obs), self._ptr(self.state), C.byref(self._c), B, R, self._ptr(masks), n,
                 row(actions_all), row(rewards_all), row(dones_all), self._ptr(self.actions), self._ptr(self.rewards),
                 self._ptr(self.dones), self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt),

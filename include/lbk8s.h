@@ -546,6 +546,10 @@ int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* c
                   float* ret32, float* ep_r32, int64_t tag0, double* log, int64_t cap, uint32_t* count,
                   void* stream);
 
+/* ---- ABI 17, additions: lb_ppo_steps64 / lb_eval_steps64 and their _supported queries, the two
+ * entry points above for envs of up to 64 endpoints (R <= 65): declared in lbk8s_abi_steps64.h, which
+ * this header includes at its end. */
+
 /* ---- Fused deep-sets training -----------------------------
  * Replaces the reference's autograd through the same modules in the PPO update
  * (envs/ppo_deepset.py:227-263 -> deep_sets_agent_original.py:56-106).  The training
@@ -682,6 +686,8 @@ typedef struct lb_set_job {
 } lb_set_job;
 int lb_ds_over_sets(const lb_set_job* jobs, int32_t num_jobs, int64_t num_sets, float* workspace,
                     int64_t workspace_floats, void* stream);
+
+#include "lbk8s_abi_steps64.h"
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,9 @@ device-to-host copy of the statistics, which waits for the device; divided by L 
 vector step) and device events around the whole call (env construction, reset, the play window, the
 result's copies).  The medians over the rounds go to the JSON file with the device and the host the
 run was on.  No speed is asserted here.
+
+With --fused-rollout-e64 the one launch is lb_eval_steps64 (run_test(e64=True)) and the shapes are
+its own: 2,000 envs of E = 64 and of E = 32 with the reject row, L = 100.
 """
 import argparse
 import json
@@ -25,6 +28,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "gym-loadbalancing_amd")]
 
 SHAPES = {"run_test_2000_envs_E6": dict(n=2000, E=6, L=100), "ppo_batch_4096_envs_E8": dict(n=4096, E=8, L=100)}
+SHAPES_E64 = {"run_test_2000_envs_E64": dict(n=2000, E=64, L=100), "run_test_2000_envs_E32": dict(n=2000, E=32, L=100)}
 
 
 def main():
@@ -33,7 +37,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--alg", choices=("dqn", "ppo"), default="dqn")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "eval_fused_ab.json"))
+    ap.add_argument("--fused-rollout-e64", action="store_true",
+                    help="the one launch through lb_eval_steps64 (run_test(e64=True)) at E = 64 and E = 32")
     args = ap.parse_args()
+    e64 = args.fused_rollout_e64
     import numpy as np
     import torch
 
@@ -49,14 +56,14 @@ def main():
                box=dict(host=platform.node(), device=prop.name, compute_units=prop.multi_processor_count,
                         torch=torch.__version__, hip=torch.version.hip),
                lib_source_hash=_native.lib().lb_source_hash().decode(), agent=args.alg, rounds=args.rounds,
-               warmup_calls_per_path=args.warmup, shapes={})
-    for name, sh in SHAPES.items():
+               warmup_calls_per_path=args.warmup, e64=e64, shapes={})
+    for name, sh in (SHAPES_E64 if e64 else SHAPES).items():
         kw = dict(num_endpoints=sh["E"], episode_length=sh["L"])
 
         def call(fused, **more):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            res = evaluate.run_test(agent, n_episodes=sh["n"], seed=42, fused=fused, **kw, **more)
+            res = evaluate.run_test(agent, n_episodes=sh["n"], seed=42, fused=fused, e64=e64, **kw, **more)
             b.record()
             b.synchronize()
             return res, a.elapsed_time(b)

@@ -30,7 +30,8 @@ from bench import CONFIGS  # noqa: E402
 
 # bench.py's scenarios and run.py's own training env (lbk8s.cli.env_kwargs: E = 6, no rejection,
 # multi reward, L = 100; with --envs 8 the reference's setup).  "default" (E = 8, rejection, R = 9)
-# and "run_py" have the one-launch PPO rollout's shape (--fused-rollout); config 4's E = 64 has not.
+# and "run_py" have the one-launch PPO rollout's shape (--fused-rollout); config 4's E = 64 has
+# lb_ppo_steps64's (--fused-rollout-e64).
 RUN_PY = dict(num_nodes=24, num_zones=4, num_endpoints=6, rejection_allowed=False, arrival_rate_r=100,
               call_duration_r=1, episode_length=100, reward_function="multi", latency_weight=1.0, cpu_weight=0.0,
               gini_weight=0.0)
@@ -60,6 +61,9 @@ def parse():
     ap.add_argument("--fused-rollout", action="store_true",
                     help="PPO: the rollout's vector steps as one launch (PPO_DeepSets(fused_rollout=True): "
                          "lb_ppo_steps; --config default or run_py, not config 4's E = 64)")
+    ap.add_argument("--fused-rollout-e64", action="store_true",
+                    help="PPO: the rollout's vector steps as one launch through lb_ppo_steps64 "
+                         "(PPO_DeepSets(fused_rollout_e64=True)): E <= 64, R <= 65, so config 4 too")
     return ap.parse_args()
 
 
@@ -108,8 +112,10 @@ def main():
         from lbk8s.ppo import PPO_DeepSets
         ppo = PPO_DeepSets(env, num_steps=args.num_steps, n_minibatches=8, update_epochs=4, ent_coef=0.001,
                            gamma=0.95, gae_lambda=0.97, seed=1, device=dev, fused_act=args.fused_act,
-                           fused_bookkeeping=args.fused_bookkeeping, fused_rollout=args.fused_rollout)
-        out.update(fused_act=ppo.fused_act, fused_bookkeeping=ppo.fused_bookkeeping, fused_rollout=ppo.fused_rollout)
+                           fused_bookkeeping=args.fused_bookkeeping, fused_rollout=args.fused_rollout,
+                           fused_rollout_e64=args.fused_rollout_e64)
+        out.update(fused_act=ppo.fused_act, fused_bookkeeping=ppo.fused_bookkeeping, fused_rollout=ppo.fused_rollout,
+                   fused_rollout_e64=ppo.fused_rollout_e64)
         next_obs = env.reset()
         next_done = torch.zeros(B, device=dev)
         for _ in range(args.warmup_updates):
