@@ -1,6 +1,6 @@
-// lbk8s_steps64.hip — the one-launch step kernels for envs of up to 64 endpoints (lbk8s_steps64.h)
-// and their entry points: lb_ppo_steps64 and lb_eval_steps64, the supersets of lb_ppo_steps and
-// lb_eval_steps (lbk8s_steps.hip).
+// lbk8s_steps64.hip — the one-launch step kernels for envs of up to 64 endpoints (lbk8s_steps64.h,
+// lbk8s_dqn64.h) and their entry points: lb_ppo_steps64, lb_eval_steps64 and lb_dqn_steps64, the
+// supersets of lb_ppo_steps, lb_eval_steps and lb_dqn_steps (lbk8s_steps.hip).
 //
 // Compiled at the end of lbk8s_ds_train.hip, the build's shortest unit (the set of units stays
 // as it was: csrc/Makefile).  Public ABI: include/lbk8s.h; the host helpers: lbk8s_host.h.
@@ -14,6 +14,7 @@
 #include "lbk8s_common.h"
 #include "lbk8s_deepsets.h"
 #include "lbk8s_steps64.h"
+#include "lbk8s_dqn64.h"
 #include "lbk8s_host.h"
 
 using namespace lbk;
@@ -29,6 +30,12 @@ bool steps64_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_element
     if (num_envs < 1 || num_envs >= WIDE_SLICE_MAX_B || cfg->rng_mode != LB_RNG_PHILOX || num_elements != A) return false;
     const Geo g = geometry(cfg, num_envs);
     return !g.tpe && g.EPL == 1 && num_elements <= STEPS64_MAX_R;
+}
+
+// lb_dqn_steps64's shape: lb_dqn_steps' (which asks neither for Philox mode nor for the action
+// count: its launch refuses those), or the rule above
+bool dqn_steps64_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    return lb_dqn_steps_supported(cfg, num_envs, num_elements) == 1 || steps64_fusable(cfg, num_envs, num_elements);
 }
 
 // (lbk8s_steps.hip's steps_record_check, with this file's entry points' names)
@@ -139,6 +146,64 @@ int lb_eval_steps64(const float* frag, float* obs, void* state, const lb_config*
     const unsigned grid = ds_grid_spread(num_envs);  // a wave per env
     LB_DISPATCH_STEPS64(g.W, ts, hipLaunchKernelGGL((k_eval_steps64<W, TS>), dim3(grid), dim3(DS_BLOCK), 0,
                                                     (hipStream_t)stream, d, e, r));
+    return check_launch();
+}
+
+int lb_dqn_steps64_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    if (validate(cfg)) return 0;
+    return dqn_steps64_fusable(cfg, num_envs, num_elements) ? 1 : 0;
+}
+
+int lb_dqn_steps64(const float* frag, float* obs, int64_t num_envs, int32_t num_elements, const uint8_t* masks,
+                   void* state, const lb_config* cfg, const lb_dqn_explore* ex, int32_t* actions_out,
+                   float* next_obs_out, float* reward_out, uint8_t* done_out, float* terminal_obs_out,
+                   double* ep_stats_out, int64_t slots, const int64_t* pos_in, int64_t* pos_out, float* rb_obs,
+                   float* rb_next_obs, int64_t* rb_actions, float* rb_rewards, float* rb_dones, double* ep_sum,
+                   double* ep_cnt, int32_t steps, int32_t* sync, void* stream) {
+    if (int r = validate(cfg)) return r;
+    if (steps < 1 || steps > 32) return fail("lb_dqn_steps64: steps must be in [1, 32]");
+    if (!sync) return fail("lb_dqn_steps64: sync (a device int32 that is 0) is required");
+    // (lb_dqn_steps' checks, under this entry point's name)
+    if (!frag || !obs || !state || !ex || !actions_out || !next_obs_out || !reward_out || !done_out || num_envs < 1)
+        return fail("lb_dqn_steps64: frag/obs/state/ex/actions/next_obs/reward/done NULL or num_envs < 1");
+    if (!ex->vstep_in || !ex->vstep_out || !ex->explore_out)
+        return fail("lb_dqn_steps64: lb_dqn_explore's device words NULL");
+    if (cfg->rng_mode != LB_RNG_PHILOX) return fail("lb_dqn_steps64 draws in Philox mode only");
+    const int32_t A = cfg->num_endpoints + (cfg->rejection_allowed ? 1 : 0);
+    if (num_elements != A) return fail("lb_dqn_steps64: num_elements must be the env's action count (R)");
+    if (slots < 1 || !pos_in || !pos_out || !rb_obs || !rb_next_obs || !rb_actions || !rb_rewards || !rb_dones ||
+        ((ep_sum || ep_cnt) && !(ep_sum && ep_cnt && ep_stats_out)))
+        return fail("lb_dqn_steps64: replay buffers NULL (or ep_sum / ep_cnt without the other or ep_stats_out)");
+    if (!dqn_steps64_fusable(cfg, num_envs, num_elements))
+        return fail("lb_dqn_steps64: the env's shape has no one-launch vector step (lb_dqn_steps64_supported)");
+    if (lb_dqn_steps_supported(cfg, num_envs, num_elements))  // the 16-lane shape: k_dqn_step
+        return lb_dqn_steps(frag, obs, num_envs, num_elements, masks, state, cfg, ex, actions_out, next_obs_out,
+                            reward_out, done_out, terminal_obs_out, ep_stats_out, slots, pos_in, pos_out, rb_obs,
+                            rb_next_obs, rb_actions, rb_rewards, rb_dones, ep_sum, ep_cnt, steps, sync, stream);
+    // (dqn_steps_launch's parameters)
+    Params e = make_params(state, cfg, num_envs);
+    e.obs = next_obs_out;
+    e.reward = reward_out;
+    e.done = done_out;
+    e.term_obs = terminal_obs_out;
+    e.ep_stats = ep_stats_out;
+    DSParams d{obs, frag, nullptr, nullptr, num_envs, num_elements, 1, 0, nullptr, nullptr, nullptr, nullptr,
+               actions_out, masks};
+    d.ex_on = 1;
+    d.ex = *ex;
+    d.ex_acc3 = e.acc3;
+    d.ex_sc = e.sc;
+    d.ex_env_offset = e.env_id_offset;
+    d.ex_key0 = e.key0;
+    d.ex_key1 = e.key1;
+    DQNReplay r{slots, num_elements * 2, pos_in, pos_out, reinterpret_cast<float4*>(obs),
+                reinterpret_cast<float4*>(rb_obs), reinterpret_cast<float4*>(rb_next_obs), rb_actions, rb_rewards,
+                rb_dones, ep_sum, ep_cnt};
+    const Geo g = geometry(cfg, num_envs);
+    const int ts = (num_elements + 15) / 16;
+    const unsigned grid = ds_grid_spread(num_envs);  // a wave per env
+    LB_DISPATCH_STEPS64(g.W, ts, hipLaunchKernelGGL((k_dqn_steps64<W, TS>), dim3(grid), dim3(DS_BLOCK), 0,
+                                                    (hipStream_t)stream, d, e, r, (int)steps, sync));
     return check_launch();
 }
 

@@ -738,6 +738,52 @@ class LBVecEnv:
             self._ptr(ep_sum), self._ptr(ep_cnt), int(n), sync.data_ptr(), self._stream()))
         return actions
 
+    def dqn_steps64_supported(self, R):
+        """Whether lb_dqn_steps64 (dqn_steps for envs of up to 64 endpoints: R <= 65 below 32,768
+        envs, Philox mode) covers this env with R-row observations; true wherever
+        dqn_steps_supported is."""
+        return bool(self._L.lb_dqn_steps64_supported(C.byref(self._c), self.num_envs, R))
+
+    def dqn_steps64(self, n, frag, obs, masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum,
+                    ep_cnt, sync):
+        """lb_dqn_steps64: dqn_steps, argument for argument, on the shapes of dqn_steps64_supported
+        (config 4's E = 64, R = 65 among them), 1 <= n <= 32; on a shape dqn_steps covers, the same
+        kernel.  masks (B, R) bool or uint8, or None (all valid); rb: the replay ring (size, obs,
+        next_obs, actions, rewards, dones); pos_in / pos_out: device addresses of the slot words."""
+        who = "dqn_steps64"
+        self._dqn_guard()
+        t = self.torch
+        B = self.num_envs
+        n = int(n)
+        if not 1 <= n <= 32:
+            raise ValueError(f"{who}: n must be in [1, 32]")
+        if not isinstance(obs, t.Tensor) or obs.dim() != 3:
+            raise ValueError(f"{who}: obs must be a (B, R, 8) tensor")
+        if (ep_sum is None) != (ep_cnt is None):
+            raise ValueError(f"{who}: ep_sum and ep_cnt go together")
+        if not isinstance(ex, _native.LBDQNExploreC):
+            raise ValueError(f"{who}: ex must be a _native.LBDQNExploreC")
+        R, S = obs.shape[1], int(rb.size)
+        mdt = masks.dtype if isinstance(masks, t.Tensor) and masks.dtype == t.uint8 else t.bool
+        self._check_tensors(who, [
+            ("frag", frag, (_native.LB_DS_FRAG_FLOATS,), t.float32, False), ("obs", obs, (B, R, 8), t.float32, False),
+            ("masks", masks, (B, R), mdt, True), ("actions", actions, (B,), t.int32, False),
+            ("next_obs", next_obs, (B, R, 8), t.float32, False), ("reward", reward, (B,), t.float32, False),
+            ("done", done, (B,), t.uint8, False), ("rb.obs", rb.obs, (S, B, R, 8), t.float32, False),
+            ("rb.next_obs", rb.next_obs, (S, B, R, 8), t.float32, False),
+            ("rb.actions", rb.actions, (S, B), t.int64, False), ("rb.rewards", rb.rewards, (S, B), t.float32, False),
+            ("rb.dones", rb.dones, (S, B), t.float32, False), ("ep_sum", ep_sum, (B,), t.float64, True),
+            ("ep_cnt", ep_cnt, (B,), t.float64, True), ("sync", sync, (1,), t.int32, False)])
+        if not self.dqn_steps64_supported(R):
+            raise RuntimeError(f"{who}: the env's shape has no one-launch vector step ({who}_supported)")
+        _native.check(self._L.lb_dqn_steps64(
+            self._ptr(frag), self._ptr(obs), B, R, self._ptr(masks), self._ptr(self.state), C.byref(self._c),
+            C.byref(ex), self._ptr(actions), self._ptr(next_obs), self._ptr(reward), self._ptr(done),
+            self._ptr(self.terminal_obs), self._ptr(self.ep_stats), S, pos_in, pos_out, self._ptr(rb.obs),
+            self._ptr(rb.next_obs), self._ptr(rb.actions), self._ptr(rb.rewards), self._ptr(rb.dones),
+            self._ptr(ep_sum), self._ptr(ep_cnt), n, self._ptr(sync), self._stream()))
+        return actions
+
     def field(self, name):
         """Env attribute as a float64 device tensor: (B, E) or (B,)."""
         shape = (self.num_envs,) if name in _native.PER_ENV_FIELDS else (self.num_envs, self.cfg.num_endpoints)

@@ -31,7 +31,8 @@ from bench import CONFIGS  # noqa: E402
 # bench.py's scenarios and run.py's own training env (lbk8s.cli.env_kwargs: E = 6, no rejection,
 # multi reward, L = 100; with --envs 8 the reference's setup).  "default" (E = 8, rejection, R = 9)
 # and "run_py" have the one-launch PPO rollout's shape (--fused-rollout); config 4's E = 64 has
-# lb_ppo_steps64's (--fused-rollout-e64).
+# lb_ppo_steps64's (--fused-rollout-e64) and, for --algo dqn --config e64_multi, lb_dqn_steps64's
+# (--dqn-steps-e64).
 RUN_PY = dict(num_nodes=24, num_zones=4, num_endpoints=6, rejection_allowed=False, arrival_rate_r=100,
               call_duration_r=1, episode_length=100, reward_function="multi", latency_weight=1.0, cpu_weight=0.0,
               gini_weight=0.0)
@@ -64,6 +65,9 @@ def parse():
     ap.add_argument("--fused-rollout-e64", action="store_true",
                     help="PPO: the rollout's vector steps as one launch through lb_ppo_steps64 "
                          "(PPO_DeepSets(fused_rollout_e64=True)): E <= 64, R <= 65, so config 4 too")
+    ap.add_argument("--dqn-steps-e64", action="store_true",
+                    help="DQN: a train period's vector steps as one launch through lb_dqn_steps64 "
+                         "(DQN_DeepSets(multi_step_e64=True)): E <= 64, R <= 65, so --config e64_multi too")
     return ap.parse_args()
 
 
@@ -149,7 +153,8 @@ def main():
         dqn = DQN_DeepSets(env, seed=1, learning_starts=min(100, args.warmup // 2), device=dev,
                            train_graph=os.environ.get("LBK8S_DQN_TRAIN_GRAPH", "1") == "1",  # (A/B switches)
                            period_graph=os.environ.get("LBK8S_DQN_PERIOD_GRAPH", "1") == "1",
-                           device_rng=os.environ.get("LBK8S_DQN_DEVICE_RNG", "1") == "1")
+                           device_rng=os.environ.get("LBK8S_DQN_DEVICE_RNG", "1") == "1",
+                           multi_step_e64=args.dqn_steps_e64)
         dqn.learn(args.warmup)
         # (the timed learn()'s period graphs captured beforehand: a one-time cost, amortised to
         # nothing over run.py's 500,000 steps; LBK8S_BENCH_PREPARE=0 times it as rounds 3-4 did)
@@ -164,6 +169,7 @@ def main():
         out.update(metric="env-steps/s including DQN training (config 5)", value=env_steps / wall,
                    unit="env-steps/s", vector_steps=args.steps, train_steps=dqn.train_steps,
                    ms_per_vector_step=wall / args.steps * 1e3,
+                   multi_step_e64=dqn.multi_step_e64,
                    buffer_slots_per_env=dqn.rb.size, train_graph=dqn.train_graph,
                    period_graph=dqn.period_graph, device_rng=dqn.device_rng,
                    graphs_captured_before_timing=os.environ.get("LBK8S_BENCH_PREPARE", "1") == "1",
