@@ -68,6 +68,15 @@ def build_parser():
                    help="--testing plays its episodes in one launch through lb_eval_steps64 "
                         "(run_test(fused=True, e64=True)): E <= 64, R <= 65, fewer than 32,768 episodes; ignored "
                         "with --test_sequential")
+    p.add_argument("--test-fused-e256", action="store_true",
+                   help="--testing plays its episodes in one launch through lb_eval_steps256 "
+                        "(run_test(fused=True, e256=True)): E <= 256, R <= 257, fewer than 32,768 episodes; ignored "
+                        "with --test_sequential")
+    p.add_argument("--test-sweep", nargs="?", const=True, default=None, type=sweep_list, metavar="E,E,...",
+                   help="--testing plays --test_episodes episodes at each of these numbers of endpoints "
+                        "(run_sweep; default 6,12,16,24,32,48,64,80,128,150,180, as run_test_deepset.py), writes "
+                        "one VecMonitor file per entry to the working directory and prints one line per entry; "
+                        "ignored with --test_sequential")
     p.add_argument("--device", default="cuda")
     p.add_argument("--seed", default=0, type=int, help="Philox seed of the envs")
     p.add_argument("--nproc", default=1, type=int, help="GPUs (ranks) to train on, one process each")
@@ -87,6 +96,37 @@ def build_parser():
                    help="dqn_deepsets: a train period's vector steps as one launch through lb_dqn_steps64 "
                         "(DQN_DeepSets(multi_step_e64=True)): E <= 64, R <= 65, fewer than 32,768 envs")
     return p
+
+
+def sweep_list(text):
+    """--test-sweep's value: a comma list of endpoint counts -> a tuple of ints."""
+    try:
+        out = tuple(int(x) for x in str(text).split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a comma list of endpoint counts: {text!r}")
+    if not out or min(out) < 1:
+        raise argparse.ArgumentTypeError(f"endpoint counts must be >= 1: {text!r}")
+    return out
+
+
+def sweep_endpoints(args):
+    """The endpoint counts --test-sweep asks for: None without the flag (or with --test_sequential,
+    which wins), evaluate.SWEEP_ENDPOINTS for the bare flag, else its list."""
+    if args.test_sweep is None or args.test_sequential:
+        return None
+    if args.test_sweep is True:
+        from .evaluate import SWEEP_ENDPOINTS
+        return SWEEP_ENDPOINTS
+    return args.test_sweep
+
+
+def eval_launch_flags(args):
+    """run_test's fused / e64 / e256 from --test-fused / --test-fused-e64 / --test-fused-e256
+    (all off with --test_sequential, which wins)."""
+    if args.test_sequential:
+        return dict(fused=False, e64=False, e256=False)
+    return dict(fused=args.test_fused or args.test_fused_e64 or args.test_fused_e256, e64=args.test_fused_e64,
+                e256=args.test_fused_e256)
 
 
 def env_kwargs(rejection, num_endpoints, num_zones, num_nodes, reward_function):
@@ -174,17 +214,27 @@ def main(argv=None):
             if rank != 0:
                 return result
     if args.testing:
-        from .evaluate import load_agent, run_sequential, run_test
+        from .evaluate import load_agent, run_sequential, run_sweep, run_test
         agent = load_agent(args.test_path, "ppo" if alg == "ppo_deepsets" else "dqn", device=args.device)
         kw = env_kwargs(args.rejection, num_endpoints, num_zones, num_nodes, reward)
         if args.test_sequential:
             from .vec_env import LBVecEnv
             env = LBVecEnv(1, device=args.device, seed=args.seed, as_tensors=True, **kw)
             res = run_sequential(agent, args.test_episodes, env)
+        elif sweep_endpoints(args) is not None:
+            kw.pop("num_endpoints")  # (the sweep's own)
+            sweep = run_sweep(agent, num_endpoints=sweep_endpoints(args), n_episodes=args.test_episodes,
+                              seed=args.seed, out_dir=".", device=args.device, **eval_launch_flags(args), **kw)
+            res = None
+            result["test_sweep"] = {}
+            for e, r in sweep.items():
+                print(f"num_endpoints {e}: mean return {float(r['r'].mean()):.6f}, wall {r['wall_s']:.3f} s")
+                result["test_sweep"][str(e)] = {"mean_return": float(r["r"].mean()), "wall_s": float(r["wall_s"])}
         else:
             res = run_test(agent, n_episodes=args.test_episodes, seed=args.seed, device=args.device,
-                           fused=args.test_fused or args.test_fused_e64, e64=args.test_fused_e64, **kw)
-        result["test_returns"] = [float(r) for r in res["r"]]
+                           **eval_launch_flags(args), **kw)
+        if res is not None:
+            result["test_returns"] = [float(r) for r in res["r"]]
     print(json.dumps(result))
     return result
 

@@ -15,7 +15,10 @@ Two forms:
   With fused=True (the CLI's --test-fused) the whole episode is one launch (lb_eval_steps: the
   argmax inside the forward kernel, the env in registers) where the env's shape has it: at most
   16 observation rows, or with e64=True (--test-fused-e64, lb_eval_steps64) at most 65 (E <= 64),
-  fewer than 32,768 envs either way.
+  or with e256=True (--test-fused-e256, lb_eval_steps256) at most 257 (E <= 256), fewer than
+  32,768 envs in every case.
+* run_sweep: run_test_deepset.py:35-36's loop over the number of endpoints (a policy trained at 6
+  endpoints played at SWEEP_ENDPOINTS), one run_test per entry, as one call.
 * run_sequential: the reference loop as written — ONE env, episodes one after another,
   DummyVecEnv's auto-reset on done followed by the loop's own reset() (so the auto-reset's
   scenario is drawn and discarded), VecMonitor's float32 episode return.  Pinned by
@@ -23,6 +26,7 @@ Two forms:
   (tests/golden/gen_golden_eval.py) replayed in trace mode.
 """
 import csv
+import os
 import time
 
 import numpy as np
@@ -70,7 +74,7 @@ def eval_image(agent, device):
 
 @torch.no_grad()
 def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", monitor_path=None, fused=False,
-             return_trace=False, e64=False, **env_kwargs):
+             return_trace=False, e64=False, e256=False, **env_kwargs):
     """Play n_episodes greedy episodes in parallel -> dict of per-episode numpy arrays:
     "r" return, "l" length, the 12 numeric info keys of the final step, and "wall_s".
 
@@ -80,14 +84,16 @@ def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", mo
     the forward kernel, the loop torch's argmax of the forward's scores: a float32 near-tie may
     resolve differently.  return_trace: also "actions" / "rewards" / "dones" (L, n), every step's.
     e64: the one launch is LBVecEnv.eval_steps64 (up to 64 endpoints: eval_steps64_supported) in
-    place of eval_steps; fused=True / None then ask that query.  False: eval_steps in every case."""
+    place of eval_steps; fused=True / None then ask that query.  False: eval_steps in every case.
+    e256: the one launch is LBVecEnv.eval_steps256 (up to 256 endpoints: eval_steps256_supported), in
+    place of either; fused=True / None then ask that query.  False: as above in every case."""
     kw = dict(TEST_ENV)
     kw.update(env_kwargs)
     env = LBVecEnv(n_episodes, device=device, seed=seed, env_id_offset=env_id_offset, auto_reset=False,
                    as_tensors=True, **kw)
     L = env.cfg.episode_length
     if fused or fused is None:
-        why = _no_one_launch(agent, env, e64)
+        why = _no_one_launch(agent, env, e64, e256)
         if why and fused:
             raise ValueError(f"run_test(fused=True): {why}")
         fused = not why
@@ -103,7 +109,8 @@ def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", mo
         _, frag = eval_image(agent, env.device)
         # (every action is always valid: action_masks() is all True, so no mask is passed; eval_steps
         # plays an episode longer than LB_EVAL_STEPS_MAX in launches of that many steps)
-        (env.eval_steps64 if e64 else env.eval_steps)(frag, obs, L, None, *(trace or ()))
+        launch = env.eval_steps256 if e256 else (env.eval_steps64 if e64 else env.eval_steps)
+        launch(frag, obs, L, None, *(trace or ()))
     else:
         t0 = time.time()
         for i in range(L):
@@ -126,12 +133,17 @@ def run_test(agent, n_episodes=2000, seed=42, env_id_offset=0, device="cuda", mo
     return out
 
 
-def _no_one_launch(agent, env, e64=False):
+def _no_one_launch(agent, env, e64=False, e256=False):
     """Why run_test cannot play `env` with `agent` in one launch (None: it can); e64: the launch
-    is eval_steps64."""
+    is eval_steps64; e256: it is eval_steps256."""
     net = (agent.actor if isinstance(agent, DeepSetAgent) else agent.q_network).net
     if not fused._geometry_ok(net, env.obs):
         return f"the fused forward does not cover this agent on {tuple(env.obs.shape)} observations"
+    if e256:
+        if not env.eval_steps256_supported(env.obs.shape[1]):
+            return (f"no one-launch evaluation for {env.num_envs} envs of {env.cfg.num_endpoints} endpoints "
+                    "(eval_steps256_supported: at most 257 observation rows, fewer than 32,768 envs)")
+        return None
     if e64:
         if not env.eval_steps64_supported(env.obs.shape[1]):
             return (f"no one-launch evaluation for {env.num_envs} envs of {env.cfg.num_endpoints} endpoints "
@@ -141,6 +153,29 @@ def _no_one_launch(agent, env, e64=False):
         return (f"no one-launch evaluation for {env.num_envs} envs of {env.cfg.num_endpoints} endpoints "
                 "(eval_steps_supported: at most 16 observation rows, fewer than 32,768 envs)")
     return None
+
+
+# run_test_deepset.py:35-36: the numbers of endpoints a policy trained at 6 is evaluated at
+SWEEP_ENDPOINTS = (6, 12, 16, 24, 32, 48, 64, 80, 128, 150, 180)
+
+
+def sweep_monitor_name(i, e):
+    """The i-th sweep entry's VecMonitor file (run_test_deepset.py:57's name)."""
+    return f"{i}_loadbalancer_gym_results_num_endpoints_{e}.monitor.csv"
+
+
+def run_sweep(agent, num_endpoints=SWEEP_ENDPOINTS, n_episodes=2000, seed=42, out_dir=None, fused=False, e64=False,
+              e256=False, **env_kwargs):
+    """The reference's evaluation sweep: for the i-th entry e of num_endpoints, run_test with
+    num_endpoints=e, the same seed and the same fused / e64 / e256 / env_kwargs -> {e: run_test's
+    dict}.  An entry equals that run_test call exactly.  out_dir: where entry i's VecMonitor file
+    (sweep_monitor_name(i, e), through write_monitor_csv) goes; None writes none."""
+    out = {}
+    for i, e in enumerate(num_endpoints):
+        path = os.path.join(out_dir, sweep_monitor_name(i, e)) if out_dir is not None else None
+        out[e] = run_test(agent, n_episodes=n_episodes, seed=seed, monitor_path=path, fused=fused, e64=e64,
+                          e256=e256, **dict(env_kwargs, num_endpoints=e))
+    return out
 
 
 @torch.no_grad()

@@ -547,6 +547,20 @@ class LBVecEnv:
         return self._eval_steps("eval_steps64", self._L.lb_eval_steps64, frag, obs, steps, masks, actions_all,
                                 rewards_all, dones_all, ep_sum, ep_cnt)
 
+    def eval_steps256_supported(self, R):
+        """Whether lb_eval_steps256 (eval_steps for envs of up to 256 endpoints: R <= 257 below
+        32,768 envs, Philox mode) covers this env with R-row observations; true wherever
+        eval_steps64_supported is."""
+        return bool(self._L.lb_eval_steps256_supported(C.byref(self._c), self.num_envs, R))
+
+    def eval_steps256(self, frag, obs, steps, masks=None, actions_all=None, rewards_all=None, dones_all=None,
+                      ep_sum=None, ep_cnt=None):
+        """lb_eval_steps256: eval_steps, argument for argument, on the shapes of
+        eval_steps256_supported (the evaluation sweep's 80, 128, 150 and 180 endpoints among them);
+        on a shape eval_steps64 covers, that entry point's kernel."""
+        return self._eval_steps("eval_steps256", self._L.lb_eval_steps256, frag, obs, steps, masks, actions_all,
+                                rewards_all, dones_all, ep_sum, ep_cnt)
+
     def eval_steps(self, frag, obs, steps, masks=None, actions_all=None, rewards_all=None, dones_all=None,
                    ep_sum=None, ep_cnt=None):
         """lb_eval_steps: `steps` greedy vector steps -- each the masked argmax of the actor-only
@@ -564,7 +578,7 @@ class LBVecEnv:
                                 rewards_all, dones_all, ep_sum, ep_cnt)
 
     def _eval_steps(self, who, entry, frag, obs, steps, masks, actions_all, rewards_all, dones_all, ep_sum, ep_cnt):
-        """eval_steps / eval_steps64 (who: the method's name, entry: its library function)."""
+        """eval_steps / eval_steps64 / eval_steps256 (who: the method's name, entry: its library function)."""
         t = self.torch
         if not self._reset_called and not t.cuda.is_current_stream_capturing():
             raise TypeError("step() called before reset()")

@@ -549,7 +549,8 @@ int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* c
 /* ---- ABI 17, additions: lb_ppo_steps64 / lb_eval_steps64 and their _supported queries, the two
  * entry points above for envs of up to 64 endpoints (R <= 65): declared in lbk8s_abi_steps64.h, which
  * this header includes at its end.  lb_dqn_steps64 and its _supported query, lb_dqn_steps for the
- * same envs: lbk8s_abi_dqn64.h, included there too. */
+ * same envs: lbk8s_abi_dqn64.h, included there too.  lb_eval_steps256 and its _supported query,
+ * lb_eval_steps for envs of up to 256 endpoints (R <= 257): lbk8s_abi_steps256.h, likewise. */
 
 /* ---- Fused deep-sets training -----------------------------
  * Replaces the reference's autograd through the same modules in the PPO update
@@ -690,6 +691,7 @@ int lb_ds_over_sets(const lb_set_job* jobs, int32_t num_jobs, int64_t num_sets, 
 
 #include "lbk8s_abi_steps64.h"
 #include "lbk8s_abi_dqn64.h"
+#include "lbk8s_abi_steps256.h"
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,9 @@ result's copies).  The medians over the rounds go to the JSON file with the devi
 run was on.  No speed is asserted here.
 
 With --fused-rollout-e64 the one launch is lb_eval_steps64 (run_test(e64=True)) and the shapes are
-its own: 2,000 envs of E = 64 and of E = 32 with the reject row, L = 100.
+its own: 2,000 envs of E = 64 and of E = 32 with the reject row, L = 100.  With --fused-e256 it is
+lb_eval_steps256 (run_test(e256=True)) at 2,000 envs of E = 80, 128, 180 and 256 with the reject
+row, L = 100: the evaluation sweep's sizes past 64 endpoints and the env's largest.
 """
 import argparse
 import json
@@ -29,6 +31,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "gym-loadbalancing_amd")]
 
 SHAPES = {"run_test_2000_envs_E6": dict(n=2000, E=6, L=100), "ppo_batch_4096_envs_E8": dict(n=4096, E=8, L=100)}
 SHAPES_E64 = {"run_test_2000_envs_E64": dict(n=2000, E=64, L=100), "run_test_2000_envs_E32": dict(n=2000, E=32, L=100)}
+SHAPES_E256 = {f"run_test_2000_envs_E{E}": dict(n=2000, E=E, L=100) for E in (80, 128, 180, 256)}
 
 
 def main():
@@ -39,8 +42,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "eval_fused_ab.json"))
     ap.add_argument("--fused-rollout-e64", action="store_true",
                     help="the one launch through lb_eval_steps64 (run_test(e64=True)) at E = 64 and E = 32")
+    ap.add_argument("--fused-e256", action="store_true",
+                    help="the one launch through lb_eval_steps256 (run_test(e256=True)) at E = 80, 128, 180 and 256")
     args = ap.parse_args()
-    e64 = args.fused_rollout_e64
+    e64, e256 = args.fused_rollout_e64, args.fused_e256
     import numpy as np
     import torch
 
@@ -56,14 +61,14 @@ def main():
                box=dict(host=platform.node(), device=prop.name, compute_units=prop.multi_processor_count,
                         torch=torch.__version__, hip=torch.version.hip),
                lib_source_hash=_native.lib().lb_source_hash().decode(), agent=args.alg, rounds=args.rounds,
-               warmup_calls_per_path=args.warmup, e64=e64, shapes={})
-    for name, sh in (SHAPES_E64 if e64 else SHAPES).items():
+               warmup_calls_per_path=args.warmup, e64=e64, e256=e256, shapes={})
+    for name, sh in (SHAPES_E256 if e256 else SHAPES_E64 if e64 else SHAPES).items():
         kw = dict(num_endpoints=sh["E"], episode_length=sh["L"])
 
         def call(fused, **more):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            res = evaluate.run_test(agent, n_episodes=sh["n"], seed=42, fused=fused, e64=e64, **kw, **more)
+            res = evaluate.run_test(agent, n_episodes=sh["n"], seed=42, fused=fused, e64=e64, e256=e256, **kw, **more)
             b.record()
             b.synchronize()
             return res, a.elapsed_time(b)
@@ -85,6 +90,7 @@ def main():
             return dict(us_per_vector_step_median=round(statistics.median(step_us[fused]), 2),
                         us_per_vector_step_min=round(min(step_us[fused]), 2),
                         us_per_vector_step_max=round(max(step_us[fused]), 2),
+                        us_per_vector_step_spread=round(max(step_us[fused]) - min(step_us[fused]), 2),
                         whole_call_ms_median=round(statistics.median(call_ms[fused]), 3))
 
         row = dict(envs=sh["n"], num_endpoints=sh["E"], obs_rows=sh["E"] + 1, episode_length=sh["L"],
