@@ -12,7 +12,7 @@
 // same waves.  Same functions, same order per env: bit for bit the three launches
 // (tests/test_gpu_dqn_step.py).  The launch takes P = 2 envs per wave iteration (lbk8s_steps.hip:
 // STEPS_P; one env per wave measured slower: profiles/r06_dqn_p1_ab.jsonl).  The per-group
-// skeleton it shares with k_ppo_steps and k_eval_steps is StepsGroup (lbk8s_steps.h).
+// skeleton it shares with k_ppo_steps and k_eval_steps is StepsEnv<16, 1, P> (lbk8s_steps.h).
 #pragma once
 
 #include "lbk8s_deepsets.h"
@@ -85,11 +85,11 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_dqn_step(DSParams d, Params e, 
     // and its next observations): the Q forward and the replay rows read them there, so a step
     // issues its stores and reads nothing back from global memory (round 6: each step waited
     // for its obs stores to land, then re-read them -- two memory round trips per step)
-    __shared__ __attribute__((aligned(16))) float4 OB[NWB][2][P * STEPS_OBS_F4];
-    float4(*ob)[P * STEPS_OBS_F4] = OB[threadIdx.x >> 6];
+    __shared__ __attribute__((aligned(16))) float4 OB[NWB][2][P * steps_obs_f4(16, 1)];
+    float4(*ob)[P * steps_obs_f4(16, 1)] = OB[threadIdx.x >> 6];
     for (int64_t gi = wave; gi < groups; gi += nwaves) {
-        StepsGroup<P> g;
-        g.open(e, nullptr, gi, lane, r.f4);  // (float4s per observation: 2 R <= STEPS_OBS_F4, host check)
+        StepsEnv<16, 1, P> g;
+        g.open(e, nullptr, gi, lane, r.f4);  // (float4s per observation: 2 R <= steps_obs_f4(16, 1), host check)
         const int64_t env0 = g.env0, env = g.env;
         for (int j = lane; j < g.j1; j += 64) ob[0][j] = r.obs[env0 * g.f4 + j];
         for (int i = 0; i < nsteps; ++i) {
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_dqn_step(DSParams d, Params e, 
             int a = 0;
             if (g.live) {
                 a = explore ? random_action(e, env, g.v.acc3, g.v.s.step) : ag;  // (exploring: :128-131)
-                if (explore && g.l16 == 0) d.actions[env] = a;
+                if (explore && g.lw == 0) d.actions[env] = a;
             }
             g.step(e, a, nxt);
             if (g.head) {

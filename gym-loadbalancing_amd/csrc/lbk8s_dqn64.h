@@ -3,7 +3,7 @@
 // 16-lane slice of R <= 16 rows only.
 //
 // One wave carries ONE env of R = 17..65 observation rows through all nsteps vector steps
-// (StepsGroupW<W, 1> of lbk8s_steps64.h), with k_dqn_step's functions in k_dqn_step's order per
+// (StepsEnv<W, 1, 1> of lbk8s_steps.h), with k_dqn_step's functions in k_dqn_step's order per
 // env: the explore mask over t .. t + nsteps - 1, the env's random action or the greedy action of
 // the Q forward (k_eval_steps64's: MODE 2, TS = ceil(R / 16) set tiles, the actor part of the
 // image), the env step, the replay rows.  Bit for bit lb_dqn_step n times, which at these shapes
@@ -11,7 +11,7 @@
 //
 // LDS.  Two observation buffers per wave, cur (step i's input) and nxt (its next observations):
 // the replay row needs both.  Over the greedy forward the env's registers are parked in nxt, which
-// is free until StepsGroupW::step writes it, and cur stays intact for the replay rows.  Bytes, 8
+// is free until StepsEnv::step writes it, and cur stays intact for the replay rows.  Bytes, 8
 // waves per block:
 //   TS = 2: actor fragments 45,056 + 2 x 8,448 = 61,952 (W = 32)
 //   TS >= 3: VG_ACTOR 39,424 + scratch 4,096 + 2 x 16,640 = 76,800 (W = 64)
@@ -28,7 +28,7 @@ template <int W, int TS>
 __global__ __launch_bounds__(DS_BLOCK, 1) void k_dqn_steps64(DSParams d, Params e, DQNReplay r, int nsteps,
                                                             int32_t* sync) {
     static_assert(TS >= 2 && TS <= 5 && 16 * (TS - 1) < W + 1, "some R <= W + 1 takes TS set tiles");
-    constexpr int NWB = DS_BLOCK / 64, OBF4 = steps64_obs_f4(W);
+    constexpr int NWB = DS_BLOCK / 64, OBF4 = steps_obs_f4(W, 1);
     constexpr bool VG = DSGeom<TS, 1, 2>::VG;
     constexpr int IMG = VG ? (int)VG_ACTOR : (int)DS_C1L;
     __shared__ __attribute__((aligned(16))) float Wt[IMG + (VG ? NWB * VG_SCRATCH : 0)];
@@ -40,23 +40,16 @@ __global__ __launch_bounds__(DS_BLOCK, 1) void k_dqn_steps64(DSParams d, Params 
     for (int i = 0; i < nsteps; ++i)
         if (dqn_explores(d.ex, t + i)) exm |= 1u << i;
     const uint32_t all = nsteps >= 32 ? ~0u : (1u << nsteps) - 1u;
-    if (exm != all) {  // (some step is greedy)
-        const float* src = d.wfrag + (VG ? DS_FLOATS : 0);
-        for (int i = threadIdx.x * 4; i < IMG; i += DS_BLOCK * 4)
-            *reinterpret_cast<float4*>(Wt + i) = *reinterpret_cast<const float4*>(src + i);
-        __syncthreads();
-    }
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* xs = VG ? Wt + IMG + wv * VG_SCRATCH : nullptr;
-    // wave-major numbering, as k_deepsets_fwd: fewer envs than waves put one wave per SIMD
-    const int64_t wave = (int64_t)wv * gridDim.x + blockIdx.x;
-    const int64_t nwaves = (int64_t)gridDim.x * NWB;
+    if (exm != all)  // (some step is greedy)
+        steps_stage_weights<IMG>(Wt, d.wfrag + (VG ? DS_FLOATS : 0));
+    const StepsWave w = steps_wave<VG, IMG>(Wt);
+    const int lane = w.lane;
+    float* xs = w.xs;
     const int R = d.R;
     const int64_t B = e.B, n4 = B * r.f4;
-    float4(*ob)[OBF4] = OB[wv];
-    for (int64_t gi = wave; gi < B; gi += nwaves) {
-        StepsGroupW<W, 1> g;
+    float4(*ob)[OBF4] = OB[w.wv];
+    for (int64_t gi = w.wave; gi < B; gi += w.nwaves) {
+        StepsEnv<W, 1, 1> g;
         g.open(e, nullptr, gi, lane, r.f4);  // (float4s per observation: 2 R <= OBF4, host check)
         const int64_t env = g.env0;
         const int f4 = g.f4;
@@ -67,24 +60,11 @@ __global__ __launch_bounds__(DS_BLOCK, 1) void k_dqn_steps64(DSParams d, Params 
             float4* cur = ob[i & 1];
             float4* nxt = ob[(i + 1) & 1];
             int a = 0;
-            if (!explore) {
-                // lb_dqn_act's greedy forward on the LDS observation (lane 0 holds the action and
-                // writes d.actions), the env parked in nxt over it
-                const int ln = steps64_lane(lane), col = ln & 15, grp = ln >> 4;
-                g.lw = ln % W;
-                float h0[TS][2], m0[2], xr0[2];
-                ds_group_obs<TS, 1, 2>(d, env, col, grp, R, h0, m0, xr0, reinterpret_cast<const float*>(cur));
-                g.park(nxt);
-                uint32_t wo = 0;  // (the weights read from LDS in every step: k_ppo_steps64)
-                asm volatile("" : "+s"(wo));
-                const float* Wc = Wt + wo;
-                const int32_t act = ds_group_actor<TS, 1, 2, VG>(d, Wc, ln, env, col, grp, R, h0, m0, xs);
-                g.lw = steps64_lane(lane) % W;
-                g.unpark(nxt);
-                a = __shfl(act, 0);
-            }
+            // lb_dqn_act's greedy forward on the LDS observation (lane 0 holds the action and writes
+            // d.actions), the env parked in nxt over it
+            if (!explore) a = steps_greedy_action<TS, VG>(d, g, Wt, xs, lane, env, R, cur, nxt);
             const int lp = steps64_lane(lane);
-            g.lw = lp % W;
+            g.relane(lp);
             if (explore && g.live) {  // (lb_dqn_act's random action of every env)
                 a = random_action(e, env, g.v.acc3, g.v.s.step);
                 if (g.head) d.actions[env] = a;

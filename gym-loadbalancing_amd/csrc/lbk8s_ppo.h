@@ -5,7 +5,7 @@
 // deep-sets forward with the categorical draw), lb_step and lb_ppo_record (the next done row, the
 // finished episodes' sums, the VecMonitor log).  Over a rollout the policy is fixed, the uniforms
 // are drawn before it starts and every output is per env, so -- as k_dqn_step does for a DQN train
-// period -- one wave carries its P envs through all the steps (StepsGroup, lbk8s_steps.h: the
+// period -- one wave carries its P envs through all the steps (StepsEnv<16, 1, P>, lbk8s_steps.h: the
 // env, the float32 running return and the episode sums in registers, the group's observations in
 // the two-buffer LDS image that the forward reads and the storage rows are copied from).  Bit for
 // bit the 3 x steps launches (tests/test_gpu_ppo_steps.py).
@@ -13,7 +13,7 @@
 // The forward is lb_ds_sample's at R <= 16: the MFMA-fragment image (DS_FLOATS, staged once per
 // block) under ds_group_obs / ds_group_actor / ds_group_critic<1, P, LB_DS_FWD_SAMPLE>.  Its
 // arithmetic is per set column, so the bits do not depend on P (lb_ds_sample itself takes P = 1,
-// 2 or 4 by the batch).  LDS: the image (135,440 B) plus 8 waves x 2 buffers x P x STEPS_OBS_F4
+// 2 or 4 by the batch).  LDS: the image (135,440 B) plus 8 waves x 2 buffers x P x 34
 // float4s = 152,848 B at P = 2 (P = 4 would pass 160 KB).
 #pragma once
 
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_ppo_steps(DSParams d, Params e,
     static_assert(P == 1 || P == 2, "envs per wave iteration (the LDS budget)");
     constexpr int NWB = DS_BLOCK / 64;
     __shared__ __attribute__((aligned(16))) float W[DS_FLOATS];
-    __shared__ __attribute__((aligned(16))) float4 OB[NWB][2][P * STEPS_OBS_F4];
+    __shared__ __attribute__((aligned(16))) float4 OB[NWB][2][P * steps_obs_f4(16, 1)];
     for (int i = threadIdx.x * 4; i < DS_FLOATS; i += DS_BLOCK * 4)
         *reinterpret_cast<float4*>(W + i) = *reinterpret_cast<const float4*>(d.wfrag + i);
     __syncthreads();
@@ -56,10 +56,10 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_ppo_steps(DSParams d, Params e,
     const int64_t nwaves = (int64_t)gridDim.x * NWB;
     const int R = d.R, col = lane & 15, grp = lane >> 4;
     const int64_t B = e.B, groups = (B + P - 1) / P;
-    float4(*ob)[P * STEPS_OBS_F4] = OB[wv];
+    float4(*ob)[P * steps_obs_f4(16, 1)] = OB[wv];
     for (int64_t gi = wave; gi < groups; gi += nwaves) {
-        StepsGroup<P> g;
-        g.open(e, &r.rec, gi, lane, 2 * R);  // (float4s per observation <= STEPS_OBS_F4: host check)
+        StepsEnv<16, 1, P> g;
+        g.open(e, &r.rec, gi, lane, 2 * R);  // (float4s per observation <= steps_obs_f4(16, 1): host check)
         const int64_t env0 = g.env0, env = g.env;
         const int f4 = g.f4;
         for (int j = lane; j < g.j1; j += 64) ob[0][j] = reinterpret_cast<const float4*>(r.obs)[env0 * f4 + j];

@@ -16,6 +16,7 @@
 #include "lbk8s_deepsets.h"
 #include "lbk8s_steps256.h"
 #include "lbk8s_host.h"
+#include "lbk8s_steps_host.h"
 
 using namespace lbk;
 
@@ -45,27 +46,16 @@ int lb_eval_steps256(const float* frag, float* obs, void* state, const lb_config
                      double* ep_stats_out, double* ep_sum, double* ep_cnt, float* ret32, float* ep_r32, int64_t tag0,
                      double* log, int64_t cap, uint32_t* count, void* stream) {
     if (int r = validate(cfg)) return r;
-    if (num_envs < 1) return fail("lb_eval_steps256: num_envs < 1");
-    if (steps < 1 || steps > LB_EVAL_STEPS_MAX) return fail("lb_eval_steps256: steps must be in [1, 4096]");
-    if (!frag || !obs || !state || !actions_out || !reward_out || !done_out || !ep_stats_out)
-        return fail("lb_eval_steps256: frag/obs/state/actions_out/reward_out/done_out/ep_stats_out NULL");
-    const StepsRecord rec{ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count};
-    if ((rec.ep_sum == nullptr) != (rec.ep_cnt == nullptr)) return fail("lb_eval_steps256: ep_sum and ep_cnt go together");
-    if (rec.log && (!rec.ret32 || !rec.count || rec.cap < 0))
-        return fail("lb_eval_steps256: a log needs ret32, count and cap >= 0");
-    if (!steps256_fusable(cfg, num_envs, num_elements))
-        return fail("lb_eval_steps256: the env's shape has no one-launch evaluation (lb_eval_steps256_supported)");
-    if (lb_eval_steps64_supported(cfg, num_envs, num_elements))  // E <= 64: k_eval_steps64 / k_eval_steps
-        return lb_eval_steps64(frag, obs, state, cfg, num_envs, num_elements, masks, steps, actions_all, rewards_all,
-                               dones_all, actions_out, reward_out, done_out, ep_stats_out, ep_sum, ep_cnt, ret32,
-                               ep_r32, tag0, log, cap, count, stream);
-    Params e = make_params(state, cfg, num_envs);
-    e.reward = reward_out;
-    e.done = done_out;
-    e.ep_stats = ep_stats_out;
-    DSParams d{nullptr, frag, nullptr, nullptr, num_envs, num_elements, 1, 0, nullptr, nullptr, nullptr, nullptr,
-               actions_out, masks};
-    EvalSteps r{steps, reinterpret_cast<float4*>(obs), actions_all, rewards_all, dones_all, rec};
+    const EvalStepsCall c{frag, obs, state, cfg, num_envs, num_elements, masks, steps, actions_all, rewards_all, dones_all,
+                          actions_out, reward_out, done_out, ep_stats_out,
+                          {ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count}, stream};
+    if (int rc = eval_steps_check("lb_eval_steps256", c)) return rc;
+    if (!steps256_fusable(cfg, num_envs, num_elements)) return steps_unsupported("lb_eval_steps256", "evaluation");
+    if (lb_eval_steps64_supported(cfg, num_envs, num_elements)) return eval_steps64_launch(c);  // E <= 64
+    DSParams d;
+    Params e;
+    EvalSteps r;
+    eval_steps_params(c, d, e, r);
     const Geo g = geometry(cfg, num_envs);
     const bool chunk = num_elements > LB_DS_MAX_ELEMENTS;  // (lb_ds_q_argmax's rule: the chunked forward)
     const unsigned grid = ds_grid_spread(num_envs);        // a wave per env

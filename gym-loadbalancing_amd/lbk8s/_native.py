@@ -18,7 +18,8 @@ SOURCES = ("lbk8s_env_steps.hip", "lbk8s_env.hip", "lbk8s_ds.hip", "lbk8s_ds_tra
            "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_steps.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "lbk8s_eval.h",
            "../../include/lbk8s.h", "../../include/lbk8s_abi_steps64.h", "../../include/lbk8s_abi_dqn64.h",
            "../../include/lbk8s_abi_steps256.h", "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_policies.hip", "lbk8s_steps64.h", "lbk8s_dqn64.h",
-           "lbk8s_steps64.hip", "lbk8s_steps256.h", "lbk8s_steps256.hip", "lbk8s_build.cpp")
+           "lbk8s_steps64.hip", "lbk8s_steps256.h", "lbk8s_steps256.hip", "lbk8s_steps_host.h",
+           "lbk8s_build.cpp")
 ABI_VERSION = 17
 
 LB_REWARD = {"naive": 0, "latency": 1, "fairness": 2, "multi": 3}

@@ -713,14 +713,18 @@ class LBVecEnv:
         finished-episode sums) -- in one launch where the shape allows it (config 5's 4096 envs),
         else as those three launches; bit for bit the same either way."""
         self._dqn_guard()
-        R = obs.shape[1]
         _native.check(self._L.lb_dqn_step(
-            frag.data_ptr(), obs.data_ptr(), self.num_envs, R, self._ptr(masks), self._ptr(self.state),
-            C.byref(self._c), C.byref(ex), self._ptr(actions), self._ptr(next_obs), self._ptr(reward), self._ptr(done),
-            self._ptr(self.terminal_obs), self._ptr(self.ep_stats), rb.size, pos_in, pos_out, rb.obs.data_ptr(),
-            rb.next_obs.data_ptr(), rb.actions.data_ptr(), rb.rewards.data_ptr(), rb.dones.data_ptr(),
-            self._ptr(ep_sum), self._ptr(ep_cnt), self._stream()))
+            *self._dqn_args(frag, obs, masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum, ep_cnt),
+            self._stream()))
         return actions
+
+    def _dqn_args(self, frag, obs, masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum, ep_cnt):
+        """lb_dqn_step's arguments up to ep_cnt, which lb_dqn_steps and lb_dqn_steps64 begin with too."""
+        return (frag.data_ptr(), obs.data_ptr(), self.num_envs, obs.shape[1], self._ptr(masks), self._ptr(self.state),
+                C.byref(self._c), C.byref(ex), self._ptr(actions), self._ptr(next_obs), self._ptr(reward),
+                self._ptr(done), self._ptr(self.terminal_obs), self._ptr(self.ep_stats), rb.size, pos_in, pos_out,
+                rb.obs.data_ptr(), rb.next_obs.data_ptr(), rb.actions.data_ptr(), rb.rewards.data_ptr(),
+                rb.dones.data_ptr(), self._ptr(ep_sum), self._ptr(ep_cnt))
 
     def _dqn_guard(self):
         """step_device's checks for the DQN step entry points (they step the env too).  A launch
@@ -743,13 +747,9 @@ class LBVecEnv:
         step counter advancing per step) in one launch; pos_in / pos_out and the explore
         struct's step words may coincide.  sync: a device int32 tensor holding 0."""
         self._dqn_guard()
-        R = obs.shape[1]
         _native.check(self._L.lb_dqn_steps(
-            frag.data_ptr(), obs.data_ptr(), self.num_envs, R, self._ptr(masks), self._ptr(self.state),
-            C.byref(self._c), C.byref(ex), self._ptr(actions), self._ptr(next_obs), self._ptr(reward), self._ptr(done),
-            self._ptr(self.terminal_obs), self._ptr(self.ep_stats), rb.size, pos_in, pos_out, rb.obs.data_ptr(),
-            rb.next_obs.data_ptr(), rb.actions.data_ptr(), rb.rewards.data_ptr(), rb.dones.data_ptr(),
-            self._ptr(ep_sum), self._ptr(ep_cnt), int(n), sync.data_ptr(), self._stream()))
+            *self._dqn_args(frag, obs, masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum, ep_cnt),
+            int(n), sync.data_ptr(), self._stream()))
         return actions
 
     def dqn_steps64_supported(self, R):
@@ -791,11 +791,8 @@ class LBVecEnv:
         if not self.dqn_steps64_supported(R):
             raise RuntimeError(f"{who}: the env's shape has no one-launch vector step ({who}_supported)")
         _native.check(self._L.lb_dqn_steps64(
-            self._ptr(frag), self._ptr(obs), B, R, self._ptr(masks), self._ptr(self.state), C.byref(self._c),
-            C.byref(ex), self._ptr(actions), self._ptr(next_obs), self._ptr(reward), self._ptr(done),
-            self._ptr(self.terminal_obs), self._ptr(self.ep_stats), S, pos_in, pos_out, self._ptr(rb.obs),
-            self._ptr(rb.next_obs), self._ptr(rb.actions), self._ptr(rb.rewards), self._ptr(rb.dones),
-            self._ptr(ep_sum), self._ptr(ep_cnt), n, self._ptr(sync), self._stream()))
+            *self._dqn_args(frag, obs, masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum, ep_cnt),
+            n, self._ptr(sync), self._stream()))
         return actions
 
     def field(self, name):
