@@ -1,6 +1,7 @@
-// lbk8s_steps256.hip — the one-launch greedy evaluation for envs of up to 256 endpoints
-// (lbk8s_steps256.h) and its entry points: lb_eval_steps256, the superset of lb_eval_steps64
-// (lbk8s_steps64.hip), and its _supported query.
+// lbk8s_steps256.hip — the one-launch greedy evaluation and DQN train period for envs of up to 256
+// endpoints (lbk8s_steps256.h, lbk8s_dqn256.h) and their entry points: lb_eval_steps256 and
+// lb_dqn_steps256, the supersets of lb_eval_steps64 and lb_dqn_steps64 (lbk8s_steps64.hip), and
+// their _supported queries.
 //
 // Compiled at the end of lbk8s_ds_train.hip, after lbk8s_steps64.hip (the set of units stays as
 // it was: csrc/Makefile).
@@ -15,6 +16,7 @@
 #include "lbk8s_common.h"
 #include "lbk8s_deepsets.h"
 #include "lbk8s_steps256.h"
+#include "lbk8s_dqn256.h"
 #include "lbk8s_host.h"
 #include "lbk8s_steps_host.h"
 
@@ -30,6 +32,12 @@ bool steps256_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elemen
     if (num_envs < 1 || num_envs >= WIDE_SLICE_MAX_B || cfg->rng_mode != LB_RNG_PHILOX || num_elements != A) return false;
     const Geo g = geometry(cfg, num_envs);
     return !g.tpe && g.W == 64 && (g.EPL == 2 || g.EPL == 4) && num_elements <= STEPS256_MAX_R;
+}
+
+// lb_dqn_steps256's shape: lb_dqn_steps64's (which asks neither for Philox mode nor for the action
+// count on the 16-lane shapes: the launch refuses those), or the rule above
+bool dqn_steps256_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    return lb_dqn_steps64_supported(cfg, num_envs, num_elements) == 1 || steps256_fusable(cfg, num_envs, num_elements);
 }
 }  // namespace
 
@@ -64,6 +72,44 @@ int lb_eval_steps256(const float* frag, float* obs, void* state, const lb_config
     else if (chunk && g.EPL == 2) hipLaunchKernelGGL((k_eval_steps256<2, true>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r);
     else if (chunk && g.EPL == 4) hipLaunchKernelGGL((k_eval_steps256<4, true>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r);
     else return fail("lb_eval_steps256: unsupported geometry");
+    return check_launch();
+}
+
+int lb_dqn_steps256_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    if (validate(cfg)) return 0;
+    return dqn_steps256_fusable(cfg, num_envs, num_elements) ? 1 : 0;
+}
+
+int lb_dqn_steps256(const float* frag, float* obs, int64_t num_envs, int32_t num_elements, const uint8_t* masks,
+                    void* state, const lb_config* cfg, const lb_dqn_explore* ex, int32_t* actions_out,
+                    float* next_obs_out, float* reward_out, uint8_t* done_out, float* terminal_obs_out,
+                    double* ep_stats_out, int64_t slots, const int64_t* pos_in, int64_t* pos_out, float* rb_obs,
+                    float* rb_next_obs, int64_t* rb_actions, float* rb_rewards, float* rb_dones, double* ep_sum,
+                    double* ep_cnt, int32_t steps, int32_t* sync, void* stream) {
+    if (int r = validate(cfg)) return r;
+    const DQNStepsCall c{frag, obs, num_envs, num_elements, masks, state, cfg, ex, actions_out, next_obs_out, reward_out,
+                         done_out, terminal_obs_out, ep_stats_out, slots, pos_in, pos_out, rb_obs, rb_next_obs,
+                         rb_actions, rb_rewards, rb_dones, ep_sum, ep_cnt, steps, sync, stream};
+    if (int rc = dqn_period_check("lb_dqn_steps256", c)) return rc;
+    if (int rc = dqn_steps_check("lb_dqn_steps256", c, false)) return rc;
+    if (!dqn_steps256_fusable(cfg, num_envs, num_elements)) return steps_unsupported("lb_dqn_steps256", "vector step");
+    if (lb_dqn_steps64_supported(cfg, num_envs, num_elements)) return dqn_steps64_launch(c);  // E <= 64
+    DSParams d;
+    Params e;
+    DQNReplay r;
+    dqn_steps_params(c, d, e, r);
+    const Geo g = geometry(cfg, num_envs);
+    const bool chunk = num_elements > LB_DS_MAX_ELEMENTS;  // (lb_ds_q_argmax's rule: the chunked forward)
+    const unsigned grid = ds_grid_spread(num_envs);        // a wave per env
+    const hipStream_t s = (hipStream_t)stream;
+    const int n = (int)steps;
+    if (!chunk && g.EPL == 2)
+        hipLaunchKernelGGL((k_dqn_steps256<2, false>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r, n, sync);
+    else if (chunk && g.EPL == 2)
+        hipLaunchKernelGGL((k_dqn_steps256<2, true>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r, n, sync);
+    else if (chunk && g.EPL == 4)
+        hipLaunchKernelGGL((k_dqn_steps256<4, true>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r, n, sync);
+    else return fail("lb_dqn_steps256: unsupported geometry");
     return check_launch();
 }
 

@@ -72,6 +72,16 @@ int eval_steps64_launch(const EvalStepsCall& c) {
     LB_LAUNCH_STEPS64(k_eval_steps64, c, d, e, r);
     return check_launch();
 }
+
+int dqn_steps64_launch(const DQNStepsCall& c) {
+    if (lb_dqn_steps_supported(c.cfg, c.num_envs, c.num_elements)) return dqn_steps_launch(c);  // the 16-lane shape
+    DSParams d;
+    Params e;
+    DQNReplay r;
+    dqn_steps_params(c, d, e, r);
+    LB_LAUNCH_STEPS64(k_dqn_steps64, c, d, e, r, (int)c.steps, c.sync);
+    return check_launch();
+}
 }  // namespace lbk
 
 extern "C" {
@@ -140,13 +150,7 @@ int lb_dqn_steps64(const float* frag, float* obs, int64_t num_envs, int32_t num_
     if (int rc = dqn_period_check("lb_dqn_steps64", c)) return rc;
     if (int rc = dqn_steps_check("lb_dqn_steps64", c, false)) return rc;
     if (!dqn_steps64_fusable(cfg, num_envs, num_elements)) return steps_unsupported("lb_dqn_steps64", "vector step");
-    if (lb_dqn_steps_supported(cfg, num_envs, num_elements)) return dqn_steps_launch(c);  // the 16-lane shape
-    DSParams d;
-    Params e;
-    DQNReplay r;
-    dqn_steps_params(c, d, e, r);
-    LB_LAUNCH_STEPS64(k_dqn_steps64, c, d, e, r, (int)c.steps, c.sync);
-    return check_launch();
+    return dqn_steps64_launch(c);
 }
 
 }  // extern "C"

@@ -81,12 +81,14 @@ struct DQNStepsCall {  // lb_dqn_steps' arguments (lb_dqn_step: steps = 1, no sy
     void* stream;
 };
 
-// The 16-lane kernels' launches of a checked call (lbk8s_steps.hip) and k_eval_steps64's, which
-// is lb_eval_steps256's at E <= 64 (lbk8s_steps64.hip; it hands the 16-lane shape on itself)
+// The 16-lane kernels' launches of a checked call (lbk8s_steps.hip) and k_eval_steps64's and
+// k_dqn_steps64's, which are lb_eval_steps256's and lb_dqn_steps256's at E <= 64 (lbk8s_steps64.hip;
+// they hand the 16-lane shape on themselves)
 int ppo_steps_launch(const PPOStepsCall& c);
 int eval_steps_launch(const EvalStepsCall& c);
 int dqn_steps_launch(const DQNStepsCall& c);
 int eval_steps64_launch(const EvalStepsCall& c);
+int dqn_steps64_launch(const DQNStepsCall& c);
 
 inline int steps_fail(const char* fn, const std::string& msg) {
     g_err = std::string(fn) + msg;
@@ -149,7 +151,7 @@ inline void eval_steps_params(const EvalStepsCall& c, DSParams& d, Params& e, Ev
     r = EvalSteps{c.steps, reinterpret_cast<float4*>(c.obs), c.actions_all, c.rewards_all, c.dones_all, c.rec};
 }
 
-// lb_dqn_steps' and lb_dqn_steps64's own arguments: the period's length and the launch's counter
+// lb_dqn_steps', lb_dqn_steps64's and lb_dqn_steps256's own arguments: the period's length and the launch's counter
 inline int dqn_period_check(const char* fn, const DQNStepsCall& c) {
     if (c.steps < 1 || c.steps > 32) return steps_fail(fn, ": steps must be in [1, 32]");
     if (!c.sync) return steps_fail(fn, ": sync (a device int32 that is 0) is required");

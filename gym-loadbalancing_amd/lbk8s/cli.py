@@ -95,6 +95,9 @@ def build_parser():
     p.add_argument("--dqn-steps-e64", action="store_true",
                    help="dqn_deepsets: a train period's vector steps as one launch through lb_dqn_steps64 "
                         "(DQN_DeepSets(multi_step_e64=True)): E <= 64, R <= 65, fewer than 32,768 envs")
+    p.add_argument("--dqn-steps-e256", action="store_true",
+                   help="dqn_deepsets: a train period's vector steps as one launch through lb_dqn_steps256 "
+                        "(DQN_DeepSets(multi_step_e256=True)): E <= 256, R <= 257, fewer than 32,768 envs")
     return p
 
 
@@ -147,19 +150,20 @@ def get_env(env_name, rejection, num_endpoints, num_zones, num_nodes, reward_fun
                     **env_kwargs(rejection, num_endpoints, num_zones, num_nodes, reward_function))
 
 
-def get_model(alg, env, rank=0, dqn_steps_e64=False, **ppo_flags):
+def get_model(alg, env, rank=0, dqn_steps_e64=False, dqn_steps_e256=False, **ppo_flags):
     """get_model (run.py:54-72) for the deep-sets algorithms.  With several ranks each rank's
     learner seed is offset by its rank, so rollout uniforms, minibatch permutations, replay
     samples and exploration coins differ across GPUs (the parameters are broadcast from rank
     0, so the replicas still start identical).  ppo_flags: PPO_DeepSets' fused_act /
-    fused_bookkeeping / fused_rollout / fused_rollout_e64 (all off by default); dqn_steps_e64:
-    DQN_DeepSets' multi_step_e64 (off by default)."""
+    fused_bookkeeping / fused_rollout / fused_rollout_e64 (all off by default); dqn_steps_e64 /
+    dqn_steps_e256: DQN_DeepSets' multi_step_e64 / multi_step_e256 (off by default)."""
     if alg == "ppo_deepsets":
         from .ppo import PPO_DeepSets
         return PPO_DeepSets(env, num_steps=100, n_minibatches=8, ent_coef=0.001, seed=2 + rank, **ppo_flags)
     if alg == "dqn_deepsets":
         from .dqn import DQN_DeepSets
-        return DQN_DeepSets(env, num_steps=100, n_minibatches=8, seed=1 + rank, multi_step_e64=dqn_steps_e64)
+        return DQN_DeepSets(env, num_steps=100, n_minibatches=8, seed=1 + rank, multi_step_e64=dqn_steps_e64,
+                            multi_step_e256=dqn_steps_e256)
     if alg in SB3_ALGS:
         raise SystemExit(f"{alg!r} is a stable-baselines3 model; this framework provides the deep-sets "
                          "algorithms (ppo_deepsets, dqn_deepsets) and LBVecEnv as a VecEnv")
@@ -199,6 +203,8 @@ def main(argv=None):
                      fused_rollout_e64=args.fused_rollout_e64) if alg == "ppo_deepsets" else {}
         if alg == "dqn_deepsets" and args.dqn_steps_e64:
             flags["dqn_steps_e64"] = True
+        if alg == "dqn_deepsets" and args.dqn_steps_e256:
+            flags["dqn_steps_e256"] = True
         model = get_model(alg, env, rank, **flags)
         if args.loading:  # resume training
             model.load(args.load_path)

@@ -151,7 +151,8 @@ class DQN_DeepSets:
                  buffer_size=10000, gamma=0.99, tau=1.0, n_minibatches: int = 4, target_network_frequency=500,
                  batch_size=128, start_e=1, end_e=0.05, exploration_fraction=0.5, learning_starts=10000,
                  train_frequency=10, device=None, log_fn=None, num_envs=None, tensorboard_log=None,
-                 train_graph=None, period_graph=None, device_rng=None, multi_step=None, multi_step_e64=False):
+                 train_graph=None, period_graph=None, device_rng=None, multi_step=None, multi_step_e64=False,
+                 multi_step_e256=False):
         # num_envs / tensorboard_log: accepted for signature compatibility with
         # dqn_deepset.py:46-67 (the env's num_envs is used; there is no tensorboard writer)
         self.env = env
@@ -223,6 +224,9 @@ class DQN_DeepSets:
         # the same for envs of up to 64 endpoints (lb_dqn_steps64: config 4's E = 64); off: every path
         # is what it was
         self.multi_step_e64 = bool(multi_step_e64)
+        # and for envs of up to 256 endpoints (lb_dqn_steps256, a superset: it serves E <= 64 too and
+        # takes precedence where both are on); off: every path is what it was
+        self.multi_step_e256 = bool(multi_step_e256)
         self._pgraphs = {}
         self._pgraph_slope = None
         # consecutive train periods replayed as ONE graph (single rank): the host's per-period
@@ -298,9 +302,17 @@ class DQN_DeepSets:
 
     def _vector_steps_dev(self, obs, masks, parity, n):
         """n vector steps from `parity`: one lb_dqn_steps launch where the env's shape has the
-        one-launch step (the Q network is fixed within a period), one lb_dqn_steps64 launch with
-        multi_step_e64 where that covers the env, else n _vector_step_dev."""
+        one-launch step (the Q network is fixed within a period), one lb_dqn_steps256 / lb_dqn_steps64
+        launch with multi_step_e256 / multi_step_e64 where that covers the env, else n
+        _vector_step_dev."""
         env, pp = self.env, self.rb.pos_pp.data_ptr()
+        if (self.multi_step_e256 and self.device.type == "cuda" and 1 <= n <= DQN_STEPS_MAX
+                and env.dqn_steps256_supported(obs.shape[1])):
+            end = parity ^ (n & 1)
+            ex = self._ex[parity] if end != parity else self._ex_same[parity]
+            env.dqn_steps256(n, self._qfrag, obs, masks, ex, self._act, self._next_obs, self._rew, self._done_u8,
+                             self.rb, pp + 8 * parity, pp + 8 * end, self._ep_sum, self._ep_cnt, self._dqn_sync)
+            return
         if (self.multi_step_e64 and self.device.type == "cuda" and 1 <= n <= DQN_STEPS_MAX
                 and env.dqn_steps64_supported(obs.shape[1])):
             end = parity ^ (n & 1)

@@ -719,7 +719,7 @@ class LBVecEnv:
         return actions
 
     def _dqn_args(self, frag, obs, masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum, ep_cnt):
-        """lb_dqn_step's arguments up to ep_cnt, which lb_dqn_steps and lb_dqn_steps64 begin with too."""
+        """lb_dqn_step's arguments up to ep_cnt, which lb_dqn_steps, lb_dqn_steps64 and lb_dqn_steps256 begin with too."""
         return (frag.data_ptr(), obs.data_ptr(), self.num_envs, obs.shape[1], self._ptr(masks), self._ptr(self.state),
                 C.byref(self._c), C.byref(ex), self._ptr(actions), self._ptr(next_obs), self._ptr(reward),
                 self._ptr(done), self._ptr(self.terminal_obs), self._ptr(self.ep_stats), rb.size, pos_in, pos_out,
@@ -764,7 +764,27 @@ class LBVecEnv:
         (config 4's E = 64, R = 65 among them), 1 <= n <= 32; on a shape dqn_steps covers, the same
         kernel.  masks (B, R) bool or uint8, or None (all valid); rb: the replay ring (size, obs,
         next_obs, actions, rewards, dones); pos_in / pos_out: device addresses of the slot words."""
-        who = "dqn_steps64"
+        return self._dqn_steps_wide("dqn_steps64", self._L.lb_dqn_steps64, self.dqn_steps64_supported, n, frag, obs, masks,
+                                    ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum, ep_cnt, sync)
+
+    def dqn_steps256_supported(self, R):
+        """Whether lb_dqn_steps256 (dqn_steps for envs of up to 256 endpoints: R <= 257 below 32,768
+        envs, Philox mode) covers this env with R-row observations; true wherever
+        dqn_steps64_supported is."""
+        return bool(self._L.lb_dqn_steps256_supported(C.byref(self._c), self.num_envs, R))
+
+    def dqn_steps256(self, n, frag, obs, masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum,
+                     ep_cnt, sync):
+        """lb_dqn_steps256: dqn_steps, argument for argument, on the shapes of dqn_steps256_supported
+        (the evaluation sweep's 80, 128, 150 and 180 endpoints among them), 1 <= n <= 32; on a shape
+        dqn_steps64 covers, the same kernel.  The arguments are dqn_steps64's."""
+        return self._dqn_steps_wide("dqn_steps256", self._L.lb_dqn_steps256, self.dqn_steps256_supported, n, frag, obs,
+                                    masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum, ep_cnt, sync)
+
+    def _dqn_steps_wide(self, who, entry, supported, n, frag, obs, masks, ex, actions, next_obs, reward, done, rb,
+                        pos_in, pos_out, ep_sum, ep_cnt, sync):
+        """dqn_steps64 / dqn_steps256 (who: the method's name, entry: its library function, supported:
+        its query): the arguments checked, then the launch."""
         self._dqn_guard()
         t = self.torch
         B = self.num_envs
@@ -788,9 +808,9 @@ class LBVecEnv:
             ("rb.actions", rb.actions, (S, B), t.int64, False), ("rb.rewards", rb.rewards, (S, B), t.float32, False),
             ("rb.dones", rb.dones, (S, B), t.float32, False), ("ep_sum", ep_sum, (B,), t.float64, True),
             ("ep_cnt", ep_cnt, (B,), t.float64, True), ("sync", sync, (1,), t.int32, False)])
-        if not self.dqn_steps64_supported(R):
+        if not supported(R):
             raise RuntimeError(f"{who}: the env's shape has no one-launch vector step ({who}_supported)")
-        _native.check(self._L.lb_dqn_steps64(
+        _native.check(entry(
             *self._dqn_args(frag, obs, masks, ex, actions, next_obs, reward, done, rb, pos_in, pos_out, ep_sum, ep_cnt),
             n, self._ptr(sync), self._stream()))
         return actions

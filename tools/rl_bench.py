@@ -32,7 +32,9 @@ from bench import CONFIGS  # noqa: E402
 # multi reward, L = 100; with --envs 8 the reference's setup).  "default" (E = 8, rejection, R = 9)
 # and "run_py" have the one-launch PPO rollout's shape (--fused-rollout); config 4's E = 64 has
 # lb_ppo_steps64's (--fused-rollout-e64) and, for --algo dqn --config e64_multi, lb_dqn_steps64's
-# (--dqn-steps-e64).
+# (--dqn-steps-e64).  --endpoints N puts N endpoints into the chosen config: --algo dqn --config
+# e64_multi --endpoints 180 is config 4's env at the evaluation sweep's largest size, which has
+# lb_dqn_steps256's shape (--dqn-steps-e256: E <= 256).
 RUN_PY = dict(num_nodes=24, num_zones=4, num_endpoints=6, rejection_allowed=False, arrival_rate_r=100,
               call_duration_r=1, episode_length=100, reward_function="multi", latency_weight=1.0, cpu_weight=0.0,
               gini_weight=0.0)
@@ -68,6 +70,11 @@ def parse():
     ap.add_argument("--dqn-steps-e64", action="store_true",
                     help="DQN: a train period's vector steps as one launch through lb_dqn_steps64 "
                          "(DQN_DeepSets(multi_step_e64=True)): E <= 64, R <= 65, so --config e64_multi too")
+    ap.add_argument("--dqn-steps-e256", action="store_true",
+                    help="DQN: a train period's vector steps as one launch through lb_dqn_steps256 "
+                         "(DQN_DeepSets(multi_step_e256=True)): E <= 256, R <= 257 (--endpoints)")
+    ap.add_argument("--endpoints", type=int, default=None,
+                    help="num_endpoints in place of the config's (its other settings kept)")
     return ap.parse_args()
 
 
@@ -98,7 +105,10 @@ def main():
     dev = torch.device("cuda", local)
     B = args.envs
     name = args.config or ("e64_multi" if args.algo == "ppo" else "default")
-    env = LBVecEnv(B, device=dev, seed=0, env_id_offset=rank * B, as_tensors=True, **RL_CONFIGS[name])
+    scenario = dict(RL_CONFIGS[name])
+    if args.endpoints is not None:
+        scenario["num_endpoints"] = args.endpoints
+    env = LBVecEnv(B, device=dev, seed=0, env_id_offset=rank * B, as_tensors=True, **scenario)
 
     def barrier_sync():
         torch.cuda.synchronize(dev)
@@ -111,7 +121,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    out = dict(algo=args.algo, config=name, envs_per_gpu=B, n_gpus=world)
+    out = dict(algo=args.algo, config=name, envs_per_gpu=B, n_gpus=world, num_endpoints=env.cfg.num_endpoints)
     if args.algo == "ppo":
         from lbk8s.ppo import PPO_DeepSets
         ppo = PPO_DeepSets(env, num_steps=args.num_steps, n_minibatches=8, update_epochs=4, ent_coef=0.001,
@@ -154,7 +164,7 @@ def main():
                            train_graph=os.environ.get("LBK8S_DQN_TRAIN_GRAPH", "1") == "1",  # (A/B switches)
                            period_graph=os.environ.get("LBK8S_DQN_PERIOD_GRAPH", "1") == "1",
                            device_rng=os.environ.get("LBK8S_DQN_DEVICE_RNG", "1") == "1",
-                           multi_step_e64=args.dqn_steps_e64)
+                           multi_step_e64=args.dqn_steps_e64, multi_step_e256=args.dqn_steps_e256)
         dqn.learn(args.warmup)
         # (the timed learn()'s period graphs captured beforehand: a one-time cost, amortised to
         # nothing over run.py's 500,000 steps; LBK8S_BENCH_PREPARE=0 times it as rounds 3-4 did)
@@ -169,7 +179,7 @@ def main():
         out.update(metric="env-steps/s including DQN training (config 5)", value=env_steps / wall,
                    unit="env-steps/s", vector_steps=args.steps, train_steps=dqn.train_steps,
                    ms_per_vector_step=wall / args.steps * 1e3,
-                   multi_step_e64=dqn.multi_step_e64,
+                   multi_step_e64=dqn.multi_step_e64, multi_step_e256=dqn.multi_step_e256,
                    buffer_slots_per_env=dqn.rb.size, train_graph=dqn.train_graph,
                    period_graph=dqn.period_graph, device_rng=dqn.device_rng,
                    graphs_captured_before_timing=os.environ.get("LBK8S_BENCH_PREPARE", "1") == "1",
