@@ -1032,7 +1032,7 @@ __device__ __forceinline__ void store_rows_chunk(float* plane, const float (&h)[
 // sample mode of the chunked forward (ds_sample_group's definition): lg[j] is the masked logit
 // of row 64 j + lane (-inf past R).  The scan of a slot is row_scan over each 16-lane row, plus
 // the totals of the rows before it and of the slots before it; the lane holding the action's
-// row writes the set's outputs.
+// row writes the set's outputs.  Every lane returns the action (k_ppo_steps256 steps the env with it).
 constexpr int DS_SLOTS = (LB_DS_MAX_ELEMENTS_FWD + 63) / 64;
 __device__ __forceinline__ float ds_wave_max(float v) {
     float a[1] = {v};
@@ -1040,7 +1040,7 @@ __device__ __forceinline__ float ds_wave_max(float v) {
     a[0] = max2(a[0], __shfl_xor(a[0], 16));
     return max2(a[0], __shfl_xor(a[0], 32));
 }
-__device__ __forceinline__ void ds_sample_wave(const DSParams& p, const float (&lg)[DS_SLOTS], int64_t env, int lane) {
+__device__ __forceinline__ int32_t ds_sample_wave(const DSParams& p, const float (&lg)[DS_SLOTS], int64_t env, int lane) {
     const int grp = lane >> 4;
     float m = lg[0];
 #pragma unroll
@@ -1067,13 +1067,14 @@ __device__ __forceinline__ void ds_sample_wave(const DSParams& p, const float (&
     }
     const float f = -ds_wave_max(-first), l = ds_wave_max(last);
     const int a = f < 1e8f ? (int)f : (int)l;
-    if (lane != (a & 63)) return;
+    if (lane != (a & 63)) return a;
     float la = lg[0];
 #pragma unroll
     for (int j = 1; j < DS_SLOTS; ++j) la = (a >> 6) == j ? lg[j] : la;
     p.actions[env] = a;
     if (p.actions_f32) p.actions_f32[env] = (float)a;
     p.logprob[env] = (la - m) - logf(run);
+    return a;
 }
 
 // MODE 0: logits / value; 1: training forward (activations, set maxima + first argmax rows,

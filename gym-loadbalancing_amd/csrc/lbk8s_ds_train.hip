@@ -203,7 +203,7 @@ int lb_ds_set_grads(const float* setvec, const float* dlogits, const float* dmea
 // this unit (the build's shortest; the set of units stays as it was: csrc/Makefile)
 #include "lbk8s_steps64.hip"
 
-// the one-launch greedy evaluation and DQN train period for envs of up to 256 endpoints and their
-// entry points, likewise
+// the one-launch greedy evaluation, DQN train period and PPO rollout for envs of up to 256 endpoints
+// and their entry points, likewise
 // (alone, this unit stays shorter with it than lbk8s_learn.hip would: DESIGN §1)
 #include "lbk8s_steps256.hip"

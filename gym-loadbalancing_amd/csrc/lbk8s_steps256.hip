@@ -1,7 +1,7 @@
-// lbk8s_steps256.hip — the one-launch greedy evaluation and DQN train period for envs of up to 256
-// endpoints (lbk8s_steps256.h, lbk8s_dqn256.h) and their entry points: lb_eval_steps256 and
-// lb_dqn_steps256, the supersets of lb_eval_steps64 and lb_dqn_steps64 (lbk8s_steps64.hip), and
-// their _supported queries.
+// lbk8s_steps256.hip — the one-launch greedy evaluation, DQN train period and PPO rollout for envs
+// of up to 256 endpoints (lbk8s_steps256.h, lbk8s_dqn256.h, lbk8s_ppo256.h) and their entry points:
+// lb_eval_steps256, lb_dqn_steps256 and lb_ppo_steps256, the supersets of lb_eval_steps64,
+// lb_dqn_steps64 and lb_ppo_steps64 (lbk8s_steps64.hip), and their _supported queries.
 //
 // Compiled at the end of lbk8s_ds_train.hip, after lbk8s_steps64.hip (the set of units stays as
 // it was: csrc/Makefile).
@@ -17,6 +17,7 @@
 #include "lbk8s_deepsets.h"
 #include "lbk8s_steps256.h"
 #include "lbk8s_dqn256.h"
+#include "lbk8s_ppo256.h"
 #include "lbk8s_host.h"
 #include "lbk8s_steps_host.h"
 
@@ -38,6 +39,12 @@ bool steps256_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elemen
 // count on the 16-lane shapes: the launch refuses those), or the rule above
 bool dqn_steps256_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
     return lb_dqn_steps64_supported(cfg, num_envs, num_elements) == 1 || steps256_fusable(cfg, num_envs, num_elements);
+}
+
+// lb_ppo_steps256's shape: lb_ppo_steps64's, or the rule above (the sampling forward in place of
+// the greedy one)
+bool ppo_steps256_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    return lb_ppo_steps64_supported(cfg, num_envs, num_elements) == 1 || steps256_fusable(cfg, num_envs, num_elements);
 }
 }  // namespace
 
@@ -110,6 +117,39 @@ int lb_dqn_steps256(const float* frag, float* obs, int64_t num_envs, int32_t num
     else if (chunk && g.EPL == 4)
         hipLaunchKernelGGL((k_dqn_steps256<4, true>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r, n, sync);
     else return fail("lb_dqn_steps256: unsupported geometry");
+    return check_launch();
+}
+
+int lb_ppo_steps256_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    if (validate(cfg)) return 0;
+    return ppo_steps256_fusable(cfg, num_envs, num_elements) ? 1 : 0;
+}
+
+int lb_ppo_steps256(const float* frag, const float* obs, void* state, const lb_config* cfg, int64_t num_envs,
+                    int32_t num_elements, int32_t steps, int32_t store_rows, const float* uniforms, float* actions_f32,
+                    float* logprobs, float* values, float* rewards, float* obs_next, float* dones_next,
+                    float* last_obs, float* last_done, int32_t* actions_out, uint8_t* done_out, double* ep_stats_out,
+                    double* ep_sum, double* ep_cnt, float* ret32, float* ep_r32, int64_t tag0, double* log, int64_t cap,
+                    uint32_t* count, void* stream) {
+    if (int r = validate(cfg)) return r;
+    const PPOStepsCall c{frag, obs, state, cfg, num_envs, num_elements, steps, store_rows, uniforms, actions_f32, logprobs,
+                         values, rewards, obs_next, dones_next, last_obs, last_done, actions_out, done_out, ep_stats_out,
+                         {ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count}, stream};
+    if (int rc = ppo_steps_check("lb_ppo_steps256", c)) return rc;
+    if (!ppo_steps256_fusable(cfg, num_envs, num_elements)) return steps_unsupported("lb_ppo_steps256", "rollout");
+    if (lb_ppo_steps64_supported(cfg, num_envs, num_elements)) return ppo_steps64_launch(c);  // E <= 64
+    DSParams d;
+    Params e;
+    PPOSteps r;
+    ppo_steps_params(c, d, e, r);
+    const Geo g = geometry(cfg, num_envs);
+    const bool chunk = num_elements > LB_DS_MAX_ELEMENTS;  // (lb_ds_sample's rule: the chunked forward)
+    const unsigned grid = ds_grid_spread(num_envs);        // a wave per env
+    const hipStream_t s = (hipStream_t)stream;
+    if (!chunk && g.EPL == 2) hipLaunchKernelGGL((k_ppo_steps256<2, false>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r);
+    else if (chunk && g.EPL == 2) hipLaunchKernelGGL((k_ppo_steps256<2, true>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r);
+    else if (chunk && g.EPL == 4) hipLaunchKernelGGL((k_ppo_steps256<4, true>), dim3(grid), dim3(DS_BLOCK), 0, s, d, e, r);
+    else return fail("lb_ppo_steps256: unsupported geometry");
     return check_launch();
 }
 

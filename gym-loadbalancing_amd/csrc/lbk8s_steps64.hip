@@ -63,6 +63,16 @@ bool dqn_steps64_fusable(const lb_config* cfg, int64_t num_envs, int32_t num_ele
 }  // namespace
 
 namespace lbk {
+int ppo_steps64_launch(const PPOStepsCall& c) {
+    if (lb_ppo_steps_supported(c.cfg, c.num_envs, c.num_elements)) return ppo_steps_launch(c);  // the 16-lane shape
+    DSParams d;
+    Params e;
+    PPOSteps r;
+    ppo_steps_params(c, d, e, r);
+    LB_LAUNCH_STEPS64(k_ppo_steps64, c, d, e, r);
+    return check_launch();
+}
+
 int eval_steps64_launch(const EvalStepsCall& c) {
     if (lb_eval_steps_supported(c.cfg, c.num_envs, c.num_elements)) return eval_steps_launch(c);  // the 16-lane shape
     DSParams d;
@@ -103,13 +113,7 @@ int lb_ppo_steps64(const float* frag, const float* obs, void* state, const lb_co
                          {ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count}, stream};
     if (int rc = ppo_steps_check("lb_ppo_steps64", c)) return rc;
     if (!steps64_fusable(cfg, num_envs, num_elements)) return steps_unsupported("lb_ppo_steps64", "rollout");
-    if (lb_ppo_steps_supported(cfg, num_envs, num_elements)) return ppo_steps_launch(c);  // the 16-lane shape
-    DSParams d;
-    Params e;
-    PPOSteps r;
-    ppo_steps_params(c, d, e, r);
-    LB_LAUNCH_STEPS64(k_ppo_steps64, c, d, e, r);
-    return check_launch();
+    return ppo_steps64_launch(c);
 }
 
 // lb_eval_steps64's shape is lb_ppo_steps64's (the greedy forward in place of the sampling one)

@@ -81,12 +81,13 @@ struct DQNStepsCall {  // lb_dqn_steps' arguments (lb_dqn_step: steps = 1, no sy
     void* stream;
 };
 
-// The 16-lane kernels' launches of a checked call (lbk8s_steps.hip) and k_eval_steps64's and
-// k_dqn_steps64's, which are lb_eval_steps256's and lb_dqn_steps256's at E <= 64 (lbk8s_steps64.hip;
-// they hand the 16-lane shape on themselves)
+// The 16-lane kernels' launches of a checked call (lbk8s_steps.hip) and k_ppo_steps64's,
+// k_eval_steps64's and k_dqn_steps64's, which are lb_ppo_steps256's, lb_eval_steps256's and
+// lb_dqn_steps256's at E <= 64 (lbk8s_steps64.hip; they hand the 16-lane shape on themselves)
 int ppo_steps_launch(const PPOStepsCall& c);
 int eval_steps_launch(const EvalStepsCall& c);
 int dqn_steps_launch(const DQNStepsCall& c);
+int ppo_steps64_launch(const PPOStepsCall& c);
 int eval_steps64_launch(const EvalStepsCall& c);
 int dqn_steps64_launch(const DQNStepsCall& c);
 

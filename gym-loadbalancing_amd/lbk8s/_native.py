@@ -17,8 +17,8 @@ SOURCES = ("lbk8s_env_steps.hip", "lbk8s_env.hip", "lbk8s_ds.hip", "lbk8s_ds_tra
            "lbk8s_learn.hip", "lbk8s_host.h", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
            "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_steps.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "lbk8s_eval.h",
            "../../include/lbk8s.h", "../../include/lbk8s_abi_steps64.h", "../../include/lbk8s_abi_dqn64.h",
-           "../../include/lbk8s_abi_steps256.h", "../../include/lbk8s_abi_dqn256.h", "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_policies.hip", "lbk8s_steps64.h", "lbk8s_dqn64.h",
-           "lbk8s_steps64.hip", "lbk8s_steps256.h", "lbk8s_dqn256.h", "lbk8s_steps256.hip", "lbk8s_steps_host.h",
+           "../../include/lbk8s_abi_steps256.h", "../../include/lbk8s_abi_dqn256.h", "../../include/lbk8s_abi_ppo256.h", "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_policies.hip", "lbk8s_steps64.h", "lbk8s_dqn64.h",
+           "lbk8s_steps64.hip", "lbk8s_steps256.h", "lbk8s_dqn256.h", "lbk8s_ppo256.h", "lbk8s_steps256.hip", "lbk8s_steps_host.h",
            "lbk8s_build.cpp")
 ABI_VERSION = 17
 
@@ -182,6 +182,11 @@ STEPS256_SYMBOLS = tuple(STEPS256_PROTOTYPES)
 DQN256_PROTOTYPES = {name.replace("_steps", "_steps256"): PROTOTYPES[name]
                      for name in ("lb_dqn_steps_supported", "lb_dqn_steps")}
 DQN256_SYMBOLS = tuple(DQN256_PROTOTYPES)
+# include/lbk8s_abi_ppo256.h's prototypes (lbk8s.h includes it last): lb_ppo_steps' twin for envs of
+# up to 256 endpoints (tests/test_ppo_steps256_host.py compares this table with that header)
+PPO256_PROTOTYPES = {name.replace("_steps", "_steps256"): PROTOTYPES[name]
+                     for name in ("lb_ppo_steps_supported", "lb_ppo_steps")}
+PPO256_SYMBOLS = tuple(PPO256_PROTOTYPES)
 
 _lib = None
 
@@ -284,7 +289,7 @@ def lib():
         f = getattr(L, name)  # (a diagnostic library's stand-in where it lacks the symbol)
         f.restype, f.argtypes = restype, argtypes
     for name, (restype, argtypes) in {**STEPS64_PROTOTYPES, **DQN64_PROTOTYPES, **STEPS256_PROTOTYPES,
-                                       **DQN256_PROTOTYPES}.items():
+                                       **DQN256_PROTOTYPES, **PPO256_PROTOTYPES}.items():
         # (a product library is built from the tree's sources, checked below, and has them; in any
         # other, calling one raises: there is no stand-in and no fallback)
         if hasattr(L, name):

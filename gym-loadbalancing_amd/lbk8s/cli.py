@@ -92,6 +92,9 @@ def build_parser():
     p.add_argument("--fused-rollout-e64", action="store_true",
                    help="ppo_deepsets: a rollout's vector steps as one launch through lb_ppo_steps64 "
                         "(PPO_DeepSets(fused_rollout_e64=True)): E <= 64, R <= 65, fewer than 32,768 envs")
+    p.add_argument("--fused-rollout-e256", action="store_true",
+                   help="ppo_deepsets: a rollout's vector steps as one launch through lb_ppo_steps256 "
+                        "(PPO_DeepSets(fused_rollout_e256=True)): E <= 256, R <= 257, fewer than 32,768 envs")
     p.add_argument("--dqn-steps-e64", action="store_true",
                    help="dqn_deepsets: a train period's vector steps as one launch through lb_dqn_steps64 "
                         "(DQN_DeepSets(multi_step_e64=True)): E <= 64, R <= 65, fewer than 32,768 envs")
@@ -155,7 +158,7 @@ def get_model(alg, env, rank=0, dqn_steps_e64=False, dqn_steps_e256=False, **ppo
     learner seed is offset by its rank, so rollout uniforms, minibatch permutations, replay
     samples and exploration coins differ across GPUs (the parameters are broadcast from rank
     0, so the replicas still start identical).  ppo_flags: PPO_DeepSets' fused_act /
-    fused_bookkeeping / fused_rollout / fused_rollout_e64 (all off by default); dqn_steps_e64 /
+    fused_bookkeeping / fused_rollout / fused_rollout_e64 / fused_rollout_e256 (all off by default); dqn_steps_e64 /
     dqn_steps_e256: DQN_DeepSets' multi_step_e64 / multi_step_e256 (off by default)."""
     if alg == "ppo_deepsets":
         from .ppo import PPO_DeepSets
@@ -200,7 +203,8 @@ def main(argv=None):
                       env_id_offset=rank * args.num_envs, monitor_file=mon)
         flags = dict(fused_act=args.fused_act, fused_bookkeeping=args.fused_bookkeeping,
                      fused_rollout=args.fused_rollout,
-                     fused_rollout_e64=args.fused_rollout_e64) if alg == "ppo_deepsets" else {}
+                     fused_rollout_e64=args.fused_rollout_e64,
+                     fused_rollout_e256=args.fused_rollout_e256) if alg == "ppo_deepsets" else {}
         if alg == "dqn_deepsets" and args.dqn_steps_e64:
             flags["dqn_steps_e64"] = True
         if alg == "dqn_deepsets" and args.dqn_steps_e256:

@@ -26,7 +26,9 @@ With fused_act and fused_bookkeeping a rollout's vector step is three launches (
 lb_step, lb_ppo_record) and GAE is one (lb_gae, gae_device); with fused_rollout the whole
 rollout's vector steps are ONE launch (lb_ppo_steps, LBVecEnv.ppo_steps) where the env's shape has
 it (E <= 16 below 32,768 envs, R <= 16), and with fused_rollout_e64 where lb_ppo_steps64 has it
-(E <= 64 below 32,768 envs, R <= 65, Philox mode: config 4).  All four flags are off by default.
+(E <= 64 below 32,768 envs, R <= 65, Philox mode: config 4), and with fused_rollout_e256 where
+lb_ppo_steps256 has it (E <= 256, R <= 257: the evaluation sweep's sizes).  All five flags are off by
+default.
 """
 import os
 import time
@@ -151,7 +153,7 @@ class PPO_DeepSets:
                  max_grad_norm: float = 0.5, target_kl: Optional[float] = None, seed: int = 1,
                  device=None, log_fn=None, num_envs=None, tensorboard_log=None, use_graphs=None,
                  fused_act: bool = False, fused_bookkeeping: bool = False, fused_rollout: bool = False,
-                 fused_rollout_e64: bool = False):
+                 fused_rollout_e64: bool = False, fused_rollout_e256: bool = False):
         # fused_act: the rollout's policy step as ONE launch (fused.deepsets_sample) that writes the
         # env's action buffer and the step's storage rows (actions, logprobs, values) directly.  Off
         # by default: a draw on a CDF boundary can pick the neighbouring row (and u = 0 never picks
@@ -170,6 +172,9 @@ class PPO_DeepSets:
         # fused_rollout_e64: fused_rollout through LBVecEnv.ppo_steps64, whose shapes reach 64
         # endpoints (ppo_steps64_supported: R <= 65 below 32,768 envs, Philox mode); where it holds,
         # fused_rollout reads True.  fused_rollout alone keeps its 16-lane meaning.  Off by default.
+        # fused_rollout_e256: the same through LBVecEnv.ppo_steps256, whose shapes reach 256 endpoints
+        # (ppo_steps256_supported: R <= 257; a superset: it serves E <= 64 too and takes precedence
+        # where both are on).  Off by default.
         # num_envs / tensorboard_log: accepted for signature compatibility with
         # ppo_deepset.py:53-75 (the env's num_envs is used; there is no tensorboard writer)
         self.env = env
@@ -232,7 +237,10 @@ class PPO_DeepSets:
         self.fused_rollout_e64 = (bool(fused_rollout_e64) and dev.type == "cuda" and hasattr(env, "ppo_steps64")
                                   and fused.sample_supported(self.agent, self.obs[0])
                                   and env.ppo_steps64_supported(R))
-        self.fused_rollout = self.fused_rollout or self.fused_rollout_e64
+        self.fused_rollout_e256 = (bool(fused_rollout_e256) and dev.type == "cuda" and hasattr(env, "ppo_steps256")
+                                   and fused.sample_supported(self.agent, self.obs[0])
+                                   and env.ppo_steps256_supported(R))
+        self.fused_rollout = self.fused_rollout or self.fused_rollout_e64 or self.fused_rollout_e256
         if self.fused_rollout:  # (its buffers are fused_bookkeeping's; GAE in one launch too)
             self.fused_bookkeeping = True
         self.advantages = self.returns = None  # the last update()'s
@@ -250,7 +258,8 @@ class PPO_DeepSets:
         if self.fused_rollout:  # one launch (per monitor flush): every storage row, the sums, the log
             self.dones[0] = next_done
             agent = self.agent
-            steps = env.ppo_steps64 if self.fused_rollout_e64 else env.ppo_steps
+            steps = (env.ppo_steps256 if self.fused_rollout_e256
+                     else env.ppo_steps64 if self.fused_rollout_e64 else env.ppo_steps)
             steps(fused.packed(agent, agent.actor.net, agent.critic), self.obs[0], self._u, self.actions,
                   self.logprobs, self.values, self.rewards, self.obs[1:], self.dones[1:], self._last_obs,
                   self._next_done, self._act, self._done_u8, self._ep_sum, self._ep_cnt)

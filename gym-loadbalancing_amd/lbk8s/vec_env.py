@@ -475,6 +475,21 @@ class LBVecEnv:
                                values, rewards, obs_next, dones_next, last_obs, last_done, actions, dones, ep_sum,
                                ep_cnt)
 
+    def ppo_steps256_supported(self, R):
+        """Whether lb_ppo_steps256 (ppo_steps for envs of up to 256 endpoints: R <= 257 below 32,768
+        envs, Philox mode) covers this env with R-row observations; true wherever
+        ppo_steps64_supported is."""
+        return bool(self._L.lb_ppo_steps256_supported(C.byref(self._c), self.num_envs, R))
+
+    def ppo_steps256(self, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next, dones_next,
+                     last_obs, last_done, actions, dones, ep_sum, ep_cnt):
+        """lb_ppo_steps256: ppo_steps, argument for argument, on the shapes of ppo_steps256_supported
+        (the evaluation sweep's 80, 128, 150 and 180 endpoints among them); on a shape ppo_steps64
+        covers, that entry point's kernel."""
+        return self._ppo_steps("ppo_steps256", self._L.lb_ppo_steps256, frag, obs, uniforms, actions_f32, logprobs,
+                               values, rewards, obs_next, dones_next, last_obs, last_done, actions, dones, ep_sum,
+                               ep_cnt)
+
     def ppo_steps(self, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next, dones_next,
                   last_obs, last_done, actions, dones, ep_sum, ep_cnt):
         """lb_ppo_steps: T = uniforms.shape[0] PPO vector steps -- each fused.deepsets_sample on the
@@ -492,7 +507,7 @@ class LBVecEnv:
 
     def _ppo_steps(self, who, entry, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next,
                    dones_next, last_obs, last_done, actions, dones, ep_sum, ep_cnt):
-        """ppo_steps / ppo_steps64 (who: the method's name, entry: its library function)."""
+        """ppo_steps / ppo_steps64 / ppo_steps256 (who: the method's name, entry: its library function)."""
         t = self.torch
         if not self._reset_called and not t.cuda.is_current_stream_capturing():
             raise TypeError("step() called before reset()")

@@ -551,7 +551,8 @@ int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* c
  * this header includes at its end.  lb_dqn_steps64 and its _supported query, lb_dqn_steps for the
  * same envs: lbk8s_abi_dqn64.h, included there too.  lb_eval_steps256 and its _supported query,
  * lb_eval_steps for envs of up to 256 endpoints (R <= 257): lbk8s_abi_steps256.h, likewise.  lb_dqn_steps256 and
- * its _supported query, lb_dqn_steps for those envs: lbk8s_abi_dqn256.h, after it. */
+ * its _supported query, lb_dqn_steps for those envs: lbk8s_abi_dqn256.h, after it.  lb_ppo_steps256 and
+ * its _supported query, lb_ppo_steps for those envs: lbk8s_abi_ppo256.h, last. */
 
 /* ---- Fused deep-sets training -----------------------------
  * Replaces the reference's autograd through the same modules in the PPO update
@@ -694,6 +695,7 @@ int lb_ds_over_sets(const lb_set_job* jobs, int32_t num_jobs, int64_t num_sets, 
 #include "lbk8s_abi_dqn64.h"
 #include "lbk8s_abi_steps256.h"
 #include "lbk8s_abi_dqn256.h"
+#include "lbk8s_abi_ppo256.h"
 
 #ifdef __cplusplus
 }

@@ -34,7 +34,8 @@ from bench import CONFIGS  # noqa: E402
 # lb_ppo_steps64's (--fused-rollout-e64) and, for --algo dqn --config e64_multi, lb_dqn_steps64's
 # (--dqn-steps-e64).  --endpoints N puts N endpoints into the chosen config: --algo dqn --config
 # e64_multi --endpoints 180 is config 4's env at the evaluation sweep's largest size, which has
-# lb_dqn_steps256's shape (--dqn-steps-e256: E <= 256).
+# lb_dqn_steps256's shape (--dqn-steps-e256: E <= 256); with --algo ppo it has lb_ppo_steps256's
+# (--fused-rollout-e256).
 RUN_PY = dict(num_nodes=24, num_zones=4, num_endpoints=6, rejection_allowed=False, arrival_rate_r=100,
               call_duration_r=1, episode_length=100, reward_function="multi", latency_weight=1.0, cpu_weight=0.0,
               gini_weight=0.0)
@@ -67,6 +68,9 @@ def parse():
     ap.add_argument("--fused-rollout-e64", action="store_true",
                     help="PPO: the rollout's vector steps as one launch through lb_ppo_steps64 "
                          "(PPO_DeepSets(fused_rollout_e64=True)): E <= 64, R <= 65, so config 4 too")
+    ap.add_argument("--fused-rollout-e256", action="store_true",
+                    help="PPO: the rollout's vector steps as one launch through lb_ppo_steps256 "
+                         "(PPO_DeepSets(fused_rollout_e256=True)): E <= 256, R <= 257 (--endpoints)")
     ap.add_argument("--dqn-steps-e64", action="store_true",
                     help="DQN: a train period's vector steps as one launch through lb_dqn_steps64 "
                          "(DQN_DeepSets(multi_step_e64=True)): E <= 64, R <= 65, so --config e64_multi too")
@@ -127,9 +131,9 @@ def main():
         ppo = PPO_DeepSets(env, num_steps=args.num_steps, n_minibatches=8, update_epochs=4, ent_coef=0.001,
                            gamma=0.95, gae_lambda=0.97, seed=1, device=dev, fused_act=args.fused_act,
                            fused_bookkeeping=args.fused_bookkeeping, fused_rollout=args.fused_rollout,
-                           fused_rollout_e64=args.fused_rollout_e64)
+                           fused_rollout_e64=args.fused_rollout_e64, fused_rollout_e256=args.fused_rollout_e256)
         out.update(fused_act=ppo.fused_act, fused_bookkeeping=ppo.fused_bookkeeping, fused_rollout=ppo.fused_rollout,
-                   fused_rollout_e64=ppo.fused_rollout_e64)
+                   fused_rollout_e64=ppo.fused_rollout_e64, fused_rollout_e256=ppo.fused_rollout_e256)
         next_obs = env.reset()
         next_done = torch.zeros(B, device=dev)
         for _ in range(args.warmup_updates):
