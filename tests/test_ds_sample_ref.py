@@ -30,13 +30,10 @@ def forward32(c):
         return s.net.q_network(s.x).numpy(), None
 
 
-def stand_in(c, kind, bug=None):
-    """The definition in float32 numpy (or broken), into NaN-filled padded buffers."""
-    s = sr.setup(c)
-    B, R = s.B, c.R
-    logits, value = forward32(c)
-    masks = sr.sample_masks(c, kind)
-    u = s.u.numpy()
+def draw32(logits, masks, u, bug=None):
+    """The header's draw in float32 numpy (or broken): (actions (B,) int64, logprob (B,) float32)
+    of float32 logits (B, R), masks (B, R) bool or None and uniforms (B,) float32."""
+    B, R = logits.shape
     l = logits if masks is None else np.where(masks, logits, np.float32(sr.HUGE_NEG))
     m = l.max(1, keepdims=True)
     e = np.exp(l - m)
@@ -58,6 +55,17 @@ def stand_in(c, kind, bug=None):
         a = (a + 1) % R
     row = np.zeros(B, np.int64) if bug == "logprob_row0" else a
     logprob = l[np.arange(B), row] - m[:, 0] - np.log(S[:, 0])
+    return a, logprob
+
+
+def stand_in(c, kind, bug=None):
+    """The definition in float32 numpy (or broken), into NaN-filled padded buffers."""
+    s = sr.setup(c)
+    B, R = s.B, c.R
+    logits, value = forward32(c)
+    masks = sr.sample_masks(c, kind)
+    u = s.u.numpy()
+    a, logprob = draw32(logits, masks, u, bug)
     got = sr.as_numpy(sr.alloc_outputs(B, R, c.heads))
     got["actions"][:B] = a
     got["actions_f32"][:B] = a
