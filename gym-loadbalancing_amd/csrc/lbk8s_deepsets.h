@@ -950,341 +950,12 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_ds_fwd_pair(DSParams a, DSParam
     else ds_fwd_body<TS, P, 1>(b, W, blockIdx.x - ga, gridDim.x - ga);
 }
 
-// ---- large sets (LB_DS_MAX_ELEMENTS < R <= LB_DS_MAX_ELEMENTS_FWD) ------------------------
-// One env per wave iteration; the set is streamed in chunks of DS_CT 16-row tiles (32 elements).  A layer
-// needs the set-wise max of its input, so each layer's max is one pass over the chunks that
-// recomputes the earlier layers of the chunk: nothing per element leaves registers, at the
-// price of layer 1 three times and layer 2 twice for the actor (R up to 257: E <= 256 with
-// the reject row).  Same fragments, same per-element math as k_deepsets_fwd.
-constexpr int DS_CT = 2;
+}  // namespace lbk
 
-template <int KS>
-__device__ __forceinline__ void chunk_max_acc(const float (&h)[DS_CT][KS], float (&acc)[KS], int row0, int col, int R) {
-#pragma unroll
-    for (int t = 0; t < DS_CT; ++t)
-        if (row0 + 16 * t + col < R)
-#pragma unroll
-            for (int k = 0; k < KS; ++k) acc[k] = max2(acc[k], h[t][k]);
-}
+// ---- large sets (LB_DS_MAX_ELEMENTS < R <= LB_DS_MAX_ELEMENTS_FWD): the chunked forward -------
+#include "lbk8s_ds_chunked.h"
 
-__device__ __forceinline__ void load_obs_chunk(const float* x, int row0, int R, int col, int grp, float (&h0)[DS_CT][2]) {
-#pragma unroll
-    for (int t = 0; t < DS_CT; ++t) {
-        const int row = row0 + 16 * t + col;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) h0[t][kk] = row < R ? x[row * 8 + 4 * kk + grp] : 0.f;
-    }
-}
-
-// training (chunked): each lane's running max of its rows per feature and the FIRST row
-// attaining it (strict > over ascending rows)
-template <int KS>
-__device__ __forceinline__ void chunk_argmax_acc(const float (&h)[DS_CT][KS], float (&v)[KS], float (&r)[KS], int row0,
-                                                 int col, int R) {
-#pragma unroll
-    for (int t = 0; t < DS_CT; ++t) {
-        const int row = row0 + 16 * t + col;
-        if (row >= R) continue;
-#pragma unroll
-        for (int k = 0; k < KS; ++k) {
-            const bool u = h[t][k] > v[k];
-            v[k] = u ? h[t][k] : v[k];
-            r[k] = u ? (float)row : r[k];
-        }
-    }
-}
-// ... then the set's max over the 16 columns (into v, every lane) and the smallest row among
-// the lanes holding it, both to setvec (feature 16q + 4grp + i of the accumulator layout)
-__device__ __forceinline__ void chunk_argmax_store(float (&v)[16], float (&r)[16], int col, int grp, float* sv,
-                                                   int off_max, int off_id) {
-    float M[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) M[k] = v[k];
-    row_reduce<true>(M);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) r[k] = v[k] == M[k] ? -r[k] : -1e9f;
-    row_reduce<true>(r);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[k] = M[k];
-    if (col != 0) return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int f0 = 16 * q + 4 * grp;
-        *reinterpret_cast<float4*>(sv + off_max + f0) = make_float4(M[4 * q], M[4 * q + 1], M[4 * q + 2], M[4 * q + 3]);
-        *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(sv + off_id) + f0) =
-            make_uint2((uint32_t)(-r[4 * q]) | ((uint32_t)(-r[4 * q + 1]) << 16),
-                       (uint32_t)(-r[4 * q + 2]) | ((uint32_t)(-r[4 * q + 3]) << 16));
-    }
-}
-// a chunk's layer output rows (accumulator layout) into plane [B][R][64]
-__device__ __forceinline__ void store_rows_chunk(float* plane, const float (&h)[DS_CT][16], int64_t env, int R, int row0,
-                                                 int col, int grp) {
-#pragma unroll
-    for (int t = 0; t < DS_CT; ++t) {
-        const int row = row0 + 16 * t + col;
-        if (row >= R) continue;
-        float* q = plane + (env * (int64_t)R + row) * 64 + 4 * grp;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) ds_stream(q + 16 * nt, h[t][4 * nt], h[t][4 * nt + 1], h[t][4 * nt + 2], h[t][4 * nt + 3]);
-    }
-}
-
-// sample mode of the chunked forward (ds_sample_group's definition): lg[j] is the masked logit
-// of row 64 j + lane (-inf past R).  The scan of a slot is row_scan over each 16-lane row, plus
-// the totals of the rows before it and of the slots before it; the lane holding the action's
-// row writes the set's outputs.  Every lane returns the action (k_ppo_steps256 steps the env with it).
-constexpr int DS_SLOTS = (LB_DS_MAX_ELEMENTS_FWD + 63) / 64;
-__device__ __forceinline__ float ds_wave_max(float v) {
-    float a[1] = {v};
-    row_reduce<true>(a);
-    a[0] = max2(a[0], __shfl_xor(a[0], 16));
-    return max2(a[0], __shfl_xor(a[0], 32));
-}
-__device__ __forceinline__ int32_t ds_sample_wave(const DSParams& p, const float (&lg)[DS_SLOTS], int64_t env, int lane) {
-    const int grp = lane >> 4;
-    float m = lg[0];
-#pragma unroll
-    for (int j = 1; j < DS_SLOTS; ++j) m = max2(m, lg[j]);
-    m = ds_wave_max(m);
-    float e[DS_SLOTS], c[DS_SLOTS], run = 0.f;
-#pragma unroll
-    for (int j = 0; j < DS_SLOTS; ++j) {
-        e[j] = __builtin_amdgcn_exp2f((lg[j] - m) * DS_LOG2E);
-        const float sc = row_scan(e[j]);
-        const float t0 = ds_read_lane(sc, 15), t1 = ds_read_lane(sc, 31), t2 = ds_read_lane(sc, 47),
-                    t3 = ds_read_lane(sc, 63);
-        const float before = grp == 0 ? 0.f : (grp == 1 ? t0 : (grp == 2 ? t0 + t1 : (t0 + t1) + t2));
-        c[j] = run + (before + sc);
-        run = run + (((t0 + t1) + t2) + t3);
-    }
-    const float thr = p.uniforms[env] * run;
-    float first = 1e9f, last = -1.f;
-#pragma unroll
-    for (int j = DS_SLOTS - 1; j >= 0; --j) {
-        const float row = (float)(64 * j + lane);
-        if (e[j] > 0.f && c[j] >= thr) first = row;
-        if (e[j] > 0.f && last < 0.f) last = row;
-    }
-    const float f = -ds_wave_max(-first), l = ds_wave_max(last);
-    const int a = f < 1e8f ? (int)f : (int)l;
-    if (lane != (a & 63)) return a;
-    float la = lg[0];
-#pragma unroll
-    for (int j = 1; j < DS_SLOTS; ++j) la = (a >> 6) == j ? lg[j] : la;
-    p.actions[env] = a;
-    if (p.actions_f32) p.actions_f32[env] = (float)a;
-    p.logprob[env] = (la - m) - logf(run);
-    return a;
-}
-
-// MODE 0: logits / value; 1: training forward (activations, set maxima + first argmax rows,
-// psi mean; as k_deepsets_fwd<.., 1>); 2: Q values and the masked greedy action (actor only);
-// 5: MODE 0 and the sampled action with its log-probability (ds_sample_wave)
-template <int MODE>
-__global__ __launch_bounds__(DS_BLOCK, 2) void k_deepsets_fwd_big(DSParams p) {
-    constexpr bool ARGMAX = MODE == 2, TRAIN = MODE == 1, SAMPLE = MODE == LB_DS_FWD_SAMPLE;
-    if (ARGMAX && p.ex_on && ds_dqn_explore(p)) return;
-    __shared__ __attribute__((aligned(16))) float W[DS_LDS_FLOATS];
-    const int nstage = (ARGMAX || !p.critic) ? DS_C1L : DS_FLOATS;
-    for (int i = threadIdx.x * 4; i < nstage; i += DS_BLOCK * 4)
-        *reinterpret_cast<float4*>(W + i) = *reinterpret_cast<const float4*>(p.wfrag + i);
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * (DS_BLOCK / 64) + (threadIdx.x >> 6);
-    const int64_t nwaves = (int64_t)gridDim.x * (DS_BLOCK / 64);
-    const int R = p.R;
-    const int col = lane & 15, grp = lane >> 4;
-    const int nch = (R + 16 * DS_CT - 1) / (16 * DS_CT);
-    for (int64_t env = wave; env < p.B; env += nwaves) {
-        const float* x = p.obs + env * (int64_t)R * 8;
-        // the weight fragments are re-read from LDS in every chunk: an opaque base pointer
-        // per chunk keeps the compiler from hoisting KiBs of loop-invariant loads into
-        // registers (which spilled to scratch)
-        // (an opaque 32-bit offset into the shared array keeps the loads ds_reads)
-        float h0[DS_CT][2], h1[DS_CT][16], h2[DS_CT][16];
-        float m0[2] = {-INFINITY, -INFINITY};
-        for (int c = 0; c < nch; ++c) {
-            load_obs_chunk(x, 16 * DS_CT * c, R, col, grp, h0);
-            chunk_max_acc<2>(h0, m0, 16 * DS_CT * c, col, R);
-        }
-        row_reduce<true>(m0);
-        float* sv = TRAIN ? p.setvec + env * (int64_t)LB_DS_SETVEC_FLOATS : nullptr;
-        if (TRAIN && col == 0) {
-            sv[LB_DSV_MAX0 + grp] = m0[0];
-            sv[LB_DSV_MAX0 + 4 + grp] = m0[1];
-        }
-        if (p.actor) {
-            float m1[16], m2[16], r1[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                m1[k] = m2[k] = -INFINITY;
-                r1[k] = 1e9f;
-            }
-            for (int c = 0; c < nch; ++c) {
-                uint32_t wo = 0;
-                asm volatile("" : "+s"(wo));
-                const float* Wc = W + wo;
-                load_obs_chunk(x, 16 * DS_CT * c, R, col, grp, h0);
-                eq_layer<DS_CT, 1, 2, 1>(Wc + DS_A1L, Wc + DS_A1G, h0, m0, h1, lane);
-                if (TRAIN) chunk_argmax_acc<16>(h1, m1, r1, 16 * DS_CT * c, col, R);
-                else chunk_max_acc<16>(h1, m1, 16 * DS_CT * c, col, R);
-            }
-            if (TRAIN) chunk_argmax_store(m1, r1, col, grp, sv, LB_DSV_MAX1A, LB_DSV_ID1A);
-            else row_reduce<true>(m1);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) r1[k] = 1e9f;
-            for (int c = 0; c < nch; ++c) {
-                uint32_t wo = 0;
-                asm volatile("" : "+s"(wo));
-                const float* Wc = W + wo;
-                load_obs_chunk(x, 16 * DS_CT * c, R, col, grp, h0);
-                eq_layer<DS_CT, 1, 2, 1>(Wc + DS_A1L, Wc + DS_A1G, h0, m0, h1, lane);
-                eq_layer<DS_CT, 1, 16, 2>(Wc + DS_A2L, Wc + DS_A2G, h1, m1, h2, lane);
-                if (TRAIN) chunk_argmax_acc<16>(h2, m2, r1, 16 * DS_CT * c, col, R);
-                else chunk_max_acc<16>(h2, m2, 16 * DS_CT * c, col, R);
-            }
-            if (TRAIN) chunk_argmax_store(m2, r1, col, grp, sv, LB_DSV_MAX2A, LB_DSV_ID2A);
-            else row_reduce<true>(m2);
-            const float* G = W + DS_A3G + 16 * grp;
-            float gl = 0.f;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) gl += G[k * 64] * m2[k];
-            gl += __shfl_xor(gl, 16);
-            gl += __shfl_xor(gl, 32);
-            float best = -INFINITY, brow = 1e9f;
-            // sample mode: the set's masked logits stay in registers for the draw, lane l keeps
-            // rows l, 64 + l, .. (row 32 c + 16 t + col is lane (col, 2 (c & 1) + t)'s slot c >> 1)
-            float lgr[DS_SLOTS];
-#pragma unroll
-            for (int j = 0; j < DS_SLOTS; ++j) lgr[j] = -INFINITY;
-            for (int c = 0; c < nch; ++c) {
-                uint32_t wo = 0;
-                asm volatile("" : "+s"(wo));
-                const float* Wc = W + wo;
-                load_obs_chunk(x, 16 * DS_CT * c, R, col, grp, h0);
-                eq_layer<DS_CT, 1, 2, 1>(Wc + DS_A1L, Wc + DS_A1G, h0, m0, h1, lane);
-                eq_layer<DS_CT, 1, 16, 2>(Wc + DS_A2L, Wc + DS_A2G, h1, m1, h2, lane);
-                if (TRAIN) {
-                    store_rows_chunk(p.save_actor, h1, env, R, 16 * DS_CT * c, col, grp);
-                    store_rows_chunk(p.save_actor + p.B * (int64_t)R * 64, h2, env, R, 16 * DS_CT * c, col, grp);
-                }
-#pragma unroll
-                for (int t = 0; t < DS_CT; ++t) {
-                    float v = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) v += Wc[DS_A3L + 16 * grp + k * 64] * h2[t][k];
-                    v += __shfl_xor(v, 16);
-                    v += __shfl_xor(v, 32);
-                    const int row = 16 * DS_CT * c + 16 * t + col;
-                    if (row >= R) continue;
-                    if (grp == 0 && p.logits) p.logits[env * R + row] = gl + v;
-                    if (SAMPLE && grp == 2 * (c & 1) + t) {
-                        const float q = (!p.masks || p.masks[env * R + row]) ? gl + v : -1e8f;
-#pragma unroll
-                        for (int j = 0; j < DS_SLOTS; ++j) lgr[j] = j == (c >> 1) ? q : lgr[j];
-                    }
-                    if (ARGMAX) {
-                        const float q = (!p.masks || p.masks[env * R + row]) ? gl + v : -1e8f;
-                        if (q > best) {  // rows ascend: the first maximum of this lane wins
-                            best = q;
-                            brow = (float)row;
-                        }
-                    }
-                }
-            }
-            if (ARGMAX) {
-                float m[1] = {best};
-                row_reduce<true>(m);
-                float cc[1] = {best == m[0] ? -brow : -1e9f};
-                row_reduce<true>(cc);
-                if (lane == 0) p.actions[env] = (int32_t)(-cc[0]);
-            }
-            if (SAMPLE) ds_sample_wave(p, lgr, env, lane);
-        }
-        if (ARGMAX || !p.critic) continue;
-        // critic: the max of c1, then the max and the sum of c2, then layer 3 / rho as above
-        float mc1[16], mc2[16], sm[16], rc[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            mc1[k] = mc2[k] = -INFINITY;
-            sm[k] = 0.f;
-            rc[k] = 1e9f;
-        }
-        for (int c = 0; c < nch; ++c) {
-            uint32_t wo = 0;
-            asm volatile("" : "+s"(wo));
-            const float* Wc = W + wo;
-            load_obs_chunk(x, 16 * DS_CT * c, R, col, grp, h0);
-            eq_layer<DS_CT, 1, 2, 2>(Wc + DS_C1L, Wc + DS_C1G, h0, m0, h1, lane);
-            if (TRAIN) chunk_argmax_acc<16>(h1, mc1, rc, 16 * DS_CT * c, col, R);
-            else chunk_max_acc<16>(h1, mc1, 16 * DS_CT * c, col, R);
-        }
-        if (TRAIN) chunk_argmax_store(mc1, rc, col, grp, sv, LB_DSV_MAX1C, LB_DSV_ID1C);
-        else row_reduce<true>(mc1);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) rc[k] = 1e9f;
-        for (int c = 0; c < nch; ++c) {
-            uint32_t wo = 0;
-            asm volatile("" : "+s"(wo));
-            const float* Wc = W + wo;
-            load_obs_chunk(x, 16 * DS_CT * c, R, col, grp, h0);
-            eq_layer<DS_CT, 1, 2, 2>(Wc + DS_C1L, Wc + DS_C1G, h0, m0, h1, lane);
-            eq_layer<DS_CT, 1, 16, 2>(Wc + DS_C2L, Wc + DS_C2G, h1, mc1, h2, lane);
-            if (TRAIN) {
-                chunk_argmax_acc<16>(h2, mc2, rc, 16 * DS_CT * c, col, R);
-                store_rows_chunk(p.save_critic, h1, env, R, 16 * DS_CT * c, col, grp);
-                store_rows_chunk(p.save_critic + p.B * (int64_t)R * 64, h2, env, R, 16 * DS_CT * c, col, grp);
-            } else {
-                chunk_max_acc<16>(h2, mc2, 16 * DS_CT * c, col, R);
-            }
-#pragma unroll
-            for (int t = 0; t < DS_CT; ++t)
-                if (16 * DS_CT * c + 16 * t + col < R)
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) sm[k] += h2[t][k];
-        }
-        if (TRAIN) chunk_argmax_store(mc2, rc, col, grp, sv, LB_DSV_MAX2C, LB_DSV_ID2C);
-        else row_reduce<true>(mc2);
-        row_reduce<false>(sm);
-        const float invR = 1.0f / (float)R;
-        float mean[16];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            dsf4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc = mfma4(W[DS_C3G + (nt * 16 + k) * 64 + lane], mc2[k], acc);
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc = mfma4(W[DS_C3L + (nt * 16 + k) * 64 + lane], sm[k] * invR, acc);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) mean[4 * nt + i] = acc[i];
-        }
-        if (TRAIN) {  // psi mean (rho runs in torch): every column holds the set's value
-            if (col == 0) {
-                float* q = p.psi_mean + env * 64 + 4 * grp;
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt)
-                    *reinterpret_cast<float4*>(q + 16 * nt) =
-                        make_float4(mean[4 * nt], mean[4 * nt + 1], mean[4 * nt + 2], mean[4 * nt + 3]);
-            }
-            continue;
-        }
-        float r1[16];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            dsf4 acc;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = W[DS_R1B + 16 * nt + 4 * grp + i];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc = mfma4(W[DS_R1W + (nt * 16 + k) * 64 + lane], mean[k], acc);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) r1[4 * nt + i] = act_elu(acc[i]);
-        }
-        dsf4 v = {W[DS_R2B], 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) v = mfma4(W[DS_R2W + k * 64 + lane], r1[k], v);
-        if (lane == 0) p.value[env] = v[0];
-    }
-}
+namespace lbk {
 
 // lb_ds_pack: one thread per fragment float
 struct DSPackRegion {

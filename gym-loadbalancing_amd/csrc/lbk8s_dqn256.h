@@ -12,8 +12,8 @@
 //
 //   instance     R          E          forward
 //   <2, false>   66..80     65..80     steps_greedy_action<5, true>, the env parked over it
-//   <2, true>    81..129    80..128    ds_chunked_argmax_lds
-//   <4, true>    130..257   129..256   ds_chunked_argmax_lds
+//   <2, true>    81..129    80..128    ds_chunked_set<2, DSRowsLds> (lbk8s_ds_chunked.h): the function
+//   <4, true>    130..257   129..256   k_deepsets_fwd_big<2> runs per set, the rows read from the LDS image
 //
 // LDS.  ONE observation buffer per wave in all three instances, as k_eval_steps256, where
 // k_dqn_steps64 keeps two (cur and nxt): two buffers of 514 float4s for 8 waves are 131,584 bytes,
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(DS_BLOCK, 1) void k_dqn_steps256(DSParams d, Params
                 if constexpr (CHUNK) {
                     const int ln = steps64_lane(lane);
                     g.relane(ln);
-                    const int32_t act = ds_chunked_argmax_lds(d, Wt, ob, env, ln, R);
+                    const int32_t act = ds_chunked_set<2>(d, Wt, Wt, DSRowsLds{ob}, env, ln, R);
                     a = __shfl(act, 0);
                 } else {
                     a = steps_greedy_action<TS, VG>(d, g, Wt, xs, lane, env, R, ob, ob);

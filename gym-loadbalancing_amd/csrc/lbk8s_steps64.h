@@ -168,11 +168,6 @@ __global__ __launch_bounds__(DS_BLOCK, 1) void k_ppo_steps64(DSParams d, Params 
     }
 }
 
-// ds_chunked_argmax_lds (lbk8s_steps256.h, which includes this header): the chunked greedy forward
-// of R > LB_DS_MAX_ELEMENTS rows
-__device__ __forceinline__ int32_t ds_chunked_argmax_lds(const DSParams& p, const float* W, const float4* ob, int64_t env,
-                                                         int lane, int R);
-
 // The body of k_eval_steps64<W, TS> (EPL = 1, CHUNK = false) and of k_eval_steps256<EPL, CHUNK>
 // (W = 64): k_eval_steps' arguments; one env of W lanes with EPL endpoints each per wave.  Wt: the
 // actor part of the forward's image (and the waves' scratch), OB: one observation buffer per wave.
@@ -203,7 +198,7 @@ __device__ __forceinline__ void eval_steps_wide(const DSParams& d, const Params&
             if constexpr (CHUNK) {
                 const int ln = steps64_lane(lane);
                 g.relane(ln);
-                const int32_t act = ds_chunked_argmax_lds(d, Wt, ob, env, ln, R);
+                const int32_t act = ds_chunked_set<2>(d, Wt, Wt, DSRowsLds{ob}, env, ln, R);
                 g.relane(steps64_lane(lane));
                 a = __shfl(act, 0);
             } else {

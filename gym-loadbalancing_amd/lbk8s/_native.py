@@ -15,7 +15,7 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 # csrc/Makefile's SRCS, in order: the library embeds the SHA-256 of their concatenation
 SOURCES = ("lbk8s_env_steps.hip", "lbk8s_env.hip", "lbk8s_ds.hip", "lbk8s_ds_train.hip", "lbk8s_steps.hip",
            "lbk8s_learn.hip", "lbk8s_host.h", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
-           "lbk8s_deepsets.h", "lbk8s_ds_train.h", "lbk8s_steps.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "lbk8s_eval.h",
+           "lbk8s_deepsets.h", "lbk8s_ds_chunked.h", "lbk8s_ds_train.h", "lbk8s_steps.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "lbk8s_eval.h",
            "../../include/lbk8s.h", "../../include/lbk8s_abi_steps64.h", "../../include/lbk8s_abi_dqn64.h",
            "../../include/lbk8s_abi_steps256.h", "../../include/lbk8s_abi_dqn256.h", "../../include/lbk8s_abi_ppo256.h", "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_policies.hip", "lbk8s_steps64.h", "lbk8s_dqn64.h",
            "lbk8s_steps64.hip", "lbk8s_steps256.h", "lbk8s_dqn256.h", "lbk8s_ppo256.h", "lbk8s_steps256.hip", "lbk8s_steps_host.h",
