@@ -46,7 +46,7 @@ struct DSParams {
     // greedy action (inference only): actions[b] = first argmax over rows of
     // (masks[b][r] ? logits[b][r] : -1e8) (dqn_deepset.py:134-142); NULL = skip
     int32_t* actions;
-    const uint8_t* masks;  // [B][R] or NULL (all valid)
+    const uint8_t* masks;  // [B][R] or NULL (all valid); DS_FWD_WHERE: the sets' flags, [B]
     // argmax mode, lb_dqn_act: the DQN's explore decision first (ex_on); exploring, every env
     // takes its uniform random action (the env state's episode / step words) and no Q value
     // is computed
@@ -63,6 +63,13 @@ struct DSParams {
     float* actions_f32;
     float* logprob;
 };
+
+// MODE 6 (lb_ds_value_where; internal: lb_ds_forward_kernel's kinds end at LB_DS_FWD_SAMPLE): MODE
+// 0's critic on the flagged sets only (p.masks holds one flag per set, p.actor is 0).  An unflagged
+// set is a dead env of its wave iteration: its rows are not read and its columns hold zeros, and
+// the arithmetic is per set column, so a flagged set's value has MODE 0's bits.
+constexpr int DS_FWD_WHERE = 6;
+static_assert(DS_FWD_WHERE > LB_DS_FWD_SAMPLE, "an internal mode beside the public kinds");
 
 // lb_dqn_act's decision: true when this launch explores (the random actions are written)
 __device__ __forceinline__ bool ds_dqn_explore(const DSParams& p) {
@@ -597,16 +604,18 @@ __device__ __forceinline__ void store_xrow(float* plane, float v, int64_t env, i
 
 // one wave iteration's P envs: the observation -> layer-1 B fragments and its set-wise max
 // (XR: the extra row R - 1 = 16 TS into xr0, features 4kk + grp, and into the max; xobs: the
-// group's observations elsewhere, env env0 + s at xobs + s R 8 -- lb_dqn_steps' LDS copy)
+// group's observations elsewhere, env env0 + s at xobs + s R 8 -- lb_dqn_steps' LDS copy; fl: the
+// group's flags, DS_FWD_WHERE only)
 template <int TS, int P, int MODE, bool XR = false>
 __device__ __forceinline__ void ds_group_obs(const DSParams& p, int64_t env0, int col, int grp, int R,
                                              float (&h0)[P * TS][2], float (&m0)[2], float (&xr0)[2],
-                                             const float* xobs = nullptr) {
+                                             const float* xobs = nullptr, uint32_t fl = ~0u) {
     constexpr bool TRAIN = MODE == 1;
     // obs -> layer-1 B fragments: k-step kk holds feature 4kk + grp of set element col
 #pragma unroll
     for (int s = 0; s < P; ++s) {
-        const bool live = env0 + s < p.B;
+        // (DS_FWD_WHERE: bit s of fl says whether env0 + s is flagged; its rows are not read otherwise)
+        const bool live = env0 + s < p.B && (MODE != DS_FWD_WHERE || ((fl >> s) & 1));
         const float* x = xobs ? xobs + s * R * 8 : p.obs + (env0 + s) * (int64_t)R * 8;
 #pragma unroll
         for (int t = 0; t < TS; ++t) {
@@ -738,11 +747,12 @@ __device__ __forceinline__ int32_t ds_group_actor(const DSParams& p, const float
 }
 
 // one wave iteration's P envs: the critic (psi = Eq ELU Eq ELU Eq, mean over the set, rho) from
-// ds_group_obs's fragments; the value / the training forward's psi mean (W, xs: as ds_group_actor)
+// ds_group_obs's fragments; the value / the training forward's psi mean (W, xs: as ds_group_actor;
+// fl: as ds_group_obs)
 template <int TS, int P, int MODE, bool VG = DSGeom<TS, P, MODE>::VG, bool XR = false>
 __device__ __forceinline__ void ds_group_critic(const DSParams& p, const float* W, int lane, int64_t env0, int col,
                                                 int grp, int R, const float (&h0)[P * TS][2], const float (&m0)[2],
-                                                float* xs = nullptr, const float* xr0 = nullptr) {
+                                                float* xs = nullptr, const float* xr0 = nullptr, uint32_t fl = ~0u) {
     constexpr bool TRAIN = MODE == 1;
     float h1[P * TS][16], m1[16], h2[P * TS][16], m2[16];
 
@@ -887,18 +897,35 @@ __device__ __forceinline__ void ds_group_critic(const DSParams& p, const float* 
     dsf4 v = {W[DS_R2B], 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 16; ++k) v = mfma4(W[DS_R2W + k * 64 + lane], r1[k], v);
-    // row 0 of the result: column c = env (c mod P)
-    if (grp == 0 && col < P && env0 + col < p.B) p.value[env0 + col] = v[0];
+    // row 0 of the result: column c = env (c mod P) (DS_FWD_WHERE: the flagged envs' only)
+    if (grp == 0 && col < P && env0 + col < p.B && (MODE != DS_FWD_WHERE || ((fl >> col) & 1)))
+        p.value[env0 + col] = v[0];
 }
 
 // MODE 0: logits / value; 1: training forward (TRAIN: activations, psi mean); 2: Q values
 // and the masked greedy action (ARGMAX; actor only); 5: MODE 0 and the sampled action with its
-// log-probability (SAMPLE: ds_sample_group; the same image regions and LDS as MODE 0)
+// log-probability (SAMPLE: ds_sample_group; the same image regions and LDS as MODE 0); 6: MODE 0's
+// value of the flagged sets, +0 for the rest (DS_FWD_WHERE, above)
 // the forward of the blocks blk = 0 .. nblk - 1 (k_deepsets_fwd: the whole grid; k_ds_fwd_pair:
 // its half of the grid), W the block's LDS weight region
 template <int TS, int P, int MODE, bool XR = false>
 __device__ __forceinline__ void ds_fwd_body(const DSParams& p, float* W, int blk, int nblk) {
-    constexpr bool ARGMAX = MODE == 2, VG = DSGeom<TS, P, MODE, XR>::VG;
+    constexpr bool ARGMAX = MODE == 2, VG = DSGeom<TS, P, MODE, XR>::VG, WHERE = MODE == DS_FWD_WHERE;
+    // lb_ds_value_where: the unflagged sets' zeros first; a block none of whose sets is flagged ends
+    // here, before the weights are staged (99 steps in 100 of a rollout: a launch and a flag read)
+    if constexpr (WHERE) {
+        const int ln = threadIdx.x & 63;
+        int any = 0;
+        for (int64_t gi = (int64_t)(threadIdx.x >> 6) * nblk + blk; gi < (p.B + P - 1) / P;
+             gi += (int64_t)nblk * (DS_BLOCK / 64)) {
+            const int64_t env = gi * P + ln;
+            if (ln >= P || env >= p.B) continue;
+            const int f = p.masks[env] != 0;
+            if (!f) p.value[env] = 0.f;
+            any |= f;
+        }
+        if (!__syncthreads_or(any)) return;
+    }
     // stage the weight image (once per block; blocks are persistent): the fragment image, or
     // the VALU image (VG: the actor's and critic's regions, rho's for the inference forward, the
     // extra-row block for XR); an actor-only launch (DQN) stages only the actor's part
@@ -926,6 +953,17 @@ __device__ __forceinline__ void ds_fwd_body(const DSParams& p, float* W, int blk
     for (int64_t gi = wave; gi < groups; gi += nwaves) {
         const int64_t env0 = gi * P;
         float h0[P * TS][2], m0[2], xr0[2];
+        if constexpr (WHERE) {  // the group's flags (wave-uniform); a group with none does no forward work
+            uint32_t fl = 0;
+#pragma unroll
+            for (int s = 0; s < P; ++s)
+                if (env0 + s < p.B && p.masks[env0 + s]) fl |= 1u << s;
+            fl = __builtin_amdgcn_readfirstlane(fl);
+            if (!fl) continue;
+            ds_group_obs<TS, P, MODE, XR>(p, env0, col, grp, R, h0, m0, xr0, nullptr, fl);
+            ds_group_critic<TS, P, MODE, VG, XR>(p, W, lane, env0, col, grp, R, h0, m0, xs, xr0, fl);
+            continue;
+        }
         ds_group_obs<TS, P, MODE, XR>(p, env0, col, grp, R, h0, m0, xr0);
         ds_group_actor<TS, P, MODE, VG, XR>(p, W, lane, env0, col, grp, R, h0, m0, xs, xr0);
         if (ARGMAX || !p.critic) continue;

@@ -61,9 +61,10 @@ DSVariant ds_forward_variant(int which, int64_t B, int R) {
 template <int MODE>
 void ds_forward_launch(const DSParams& p, hipStream_t s) {
     static_assert(MODE == LB_DS_FWD || MODE == LB_DS_FWD_TRAIN || MODE == LB_DS_FWD_ARGMAX ||
-                      MODE == LB_DS_FWD_SAMPLE,
-                  "k_deepsets_fwd's MODE is lb_ds_forward_kernel's `which`");
-    const DSVariant v = ds_forward_variant(MODE, p.B, p.R);
+                      MODE == LB_DS_FWD_SAMPLE || MODE == DS_FWD_WHERE,
+                  "k_deepsets_fwd's MODE is lb_ds_forward_kernel's `which` (or the flagged LB_DS_FWD)");
+    // (the flagged forward is LB_DS_FWD's code on the flagged sets: its variant at the same shape)
+    const DSVariant v = ds_forward_variant(MODE == DS_FWD_WHERE ? (int)LB_DS_FWD : MODE, p.B, p.R);
     if (v.ts == 0) {
         hipLaunchKernelGGL((k_deepsets_fwd_big<MODE>), dim3(ds_grid(p.B)), dim3(DS_BLOCK), 0, s, p);
         return;
@@ -114,6 +115,19 @@ int lb_ds_forward(const float* frag, const float* obs, int64_t num_envs, int32_t
     DSParams p{obs, frag, logits_out, value_out, num_envs, num_elements, logits_out != nullptr, value_out != nullptr,
                nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     ds_forward_launch<0>(p, (hipStream_t)stream);
+    return check_launch();
+}
+
+int lb_ds_value_where(const float* frag, const float* obs, const uint8_t* flags, int64_t num_envs,
+                      int32_t num_elements, float* value_out, void* stream) {
+    if (!frag || !obs || !flags || !value_out || num_envs < 1)
+        return fail("lb_ds_value_where: frag/obs/flags/value_out NULL or num_envs < 1");
+    if (num_elements < 1 || num_elements > LB_DS_MAX_ELEMENTS_FWD)
+        return fail("lb_ds_value_where: num_elements must be in [1, 257] (LB_DS_MAX_ELEMENTS_FWD)");
+    // lb_ds_forward's parameters with logits_out NULL (the critic alone); the flags ride in masks
+    DSParams p{obs, frag, nullptr, value_out, num_envs, num_elements, 0, 1,
+               nullptr, nullptr, nullptr, nullptr, nullptr, flags};
+    ds_forward_launch<DS_FWD_WHERE>(p, (hipStream_t)stream);
     return check_launch();
 }
 

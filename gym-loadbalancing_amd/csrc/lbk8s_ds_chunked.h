@@ -169,7 +169,8 @@ __device__ __forceinline__ int32_t ds_sample_wave(const DSParams& p, const float
 // The forward of set env (R rows, read through rows) by one wave; W / We: see the head of the file.
 // MODE 0: logits / value; 1: training forward (activations, set maxima + first argmax rows,
 // psi mean; as k_deepsets_fwd<.., 1>); 2: Q values and the masked greedy action (actor only);
-// 5: MODE 0 and the sampled action with its log-probability (ds_sample_wave).
+// 5: MODE 0 and the sampled action with its log-probability (ds_sample_wave); 6 (DS_FWD_WHERE,
+// k_deepsets_fwd_big skips the unflagged sets): MODE 0.
 // Rows::HEADS_FROM_PARAMS: p.actor / p.critic / p.logits choose the heads and the logits row at run
 // time, as in the tiled forwards; the step kernels' sets (DSRowsLds) run the actor, the critic with
 // the draw (MODE 5: PPO) and write no logits row, whatever p says, so their code holds no such test
@@ -383,6 +384,17 @@ template <int MODE>
 __global__ __launch_bounds__(DS_BLOCK, 2) void k_deepsets_fwd_big(DSParams p) {
     constexpr bool ARGMAX = MODE == 2;
     if (ARGMAX && p.ex_on && ds_dqn_explore(p)) return;
+    if constexpr (MODE == DS_FWD_WHERE) {  // (as ds_fwd_body: the zeros, and no staging without a flagged set)
+        int any = 0;
+        for (int64_t env = (int64_t)blockIdx.x * (DS_BLOCK / 64) + (threadIdx.x >> 6); env < p.B;
+             env += (int64_t)gridDim.x * (DS_BLOCK / 64)) {
+            if (threadIdx.x & 63) continue;
+            const int f = p.masks[env] != 0;
+            if (!f) p.value[env] = 0.f;
+            any |= f;
+        }
+        if (!__syncthreads_or(any)) return;
+    }
     __shared__ __attribute__((aligned(16))) float W[DS_LDS_FLOATS];
     const int nstage = (ARGMAX || !p.critic) ? DS_C1L : DS_FLOATS;
     for (int i = threadIdx.x * 4; i < nstage; i += DS_BLOCK * 4)
@@ -392,8 +404,11 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_deepsets_fwd_big(DSParams p) {
     const int64_t wave = (int64_t)blockIdx.x * (DS_BLOCK / 64) + (threadIdx.x >> 6);
     const int64_t nwaves = (int64_t)gridDim.x * (DS_BLOCK / 64);
     const int R = p.R;
-    for (int64_t env = wave; env < p.B; env += nwaves)
+    for (int64_t env = wave; env < p.B; env += nwaves) {
+        if constexpr (MODE == DS_FWD_WHERE)  // (wave-uniform: an unflagged set does no forward work)
+            if (!__builtin_amdgcn_readfirstlane((int)p.masks[env])) continue;
         ds_chunked_set<MODE>(p, W, W, DSRowsGlobal{p.obs + env * (int64_t)R * 8}, env, lane, R);
+    }
 }
 
 }  // namespace lbk

@@ -223,6 +223,50 @@ __global__ __launch_bounds__(GAE_BLOCK) void k_gae(GAEParams p) {
     }
 }
 
+// lb_gae_tl: k_gae with the bootstrap at a time limit (include/lbk8s_abi_ppo_tl.h): where the step
+// ended the episode (nd != 0) the TD error takes the terminal observation's value, term_values[t],
+// in place of values[t + 1] (the next episode's first value), and the lambda-chain is cut as in
+// k_gae.  g * bv in place of (g * nv) * nnt: with term_values zero, or no done set, k_gae's bits.
+__device__ __forceinline__ void gae_tl_step(const GAEParams& p, float r, float v, float tv, float& nv, float& nd,
+                                            float& last, int64_t idx) {
+    const float bv = nd != 0.f ? tv : nv;
+    const float nnt = 1.f - nd;
+    const float delta = (r + p.g * bv) - v;
+    last = delta + (p.gl * nnt) * last;
+    p.adv[idx] = last;
+    p.ret[idx] = last + v;
+    nv = v;
+}
+
+__global__ __launch_bounds__(GAE_BLOCK) void k_gae_tl(GAEParams p, const float* term_values) {
+    const int64_t b = (int64_t)blockIdx.x * GAE_BLOCK + threadIdx.x;
+    if (b >= p.B) return;
+    float nv = p.next_value[b], nd = p.next_done[b], last = 0.f;
+    int64_t t = p.T - 1;
+    for (; t >= GAE_UNROLL - 1; t -= GAE_UNROLL) {
+        float r[GAE_UNROLL], v[GAE_UNROLL], d[GAE_UNROLL], tv[GAE_UNROLL];
+#pragma unroll
+        for (int k = 0; k < GAE_UNROLL; ++k) {
+            const int64_t idx = (t - k) * p.B + b;
+            r[k] = p.rewards[idx];
+            v[k] = p.values[idx];
+            d[k] = p.dones[idx];
+            tv[k] = term_values[idx];
+        }
+#pragma unroll
+        for (int k = 0; k < GAE_UNROLL; ++k) {
+            gae_tl_step(p, r[k], v[k], tv[k], nv, nd, last, (t - k) * p.B + b);
+            nd = d[k];
+        }
+    }
+    for (; t >= 0; --t) {
+        const int64_t idx = t * p.B + b;
+        const float r = p.rewards[idx], v = p.values[idx], d = p.dones[idx], tv = term_values[idx];
+        gae_tl_step(p, r, v, tv, nv, nd, last, idx);
+        nd = d;
+    }
+}
+
 }  // namespace lbk
 
 using namespace lbk;
@@ -307,6 +351,24 @@ int lb_gae(const float* rewards, const float* values, const float* dones, const 
     const int64_t blocks = (num_envs + GAE_BLOCK - 1) / GAE_BLOCK;
     if (blocks > 0x7FFFFFFF) return fail("lb_gae: num_envs too large for one launch");
     hipLaunchKernelGGL(k_gae, dim3((unsigned)blocks), dim3(GAE_BLOCK), 0, (hipStream_t)stream, p);
+    return check_launch();
+}
+
+int lb_gae_tl(const float* rewards, const float* values, const float* dones, const float* next_value,
+              const float* next_done, const float* term_values, int64_t num_steps, int64_t num_envs, double gamma,
+              double gae_lambda, float* advantages_out, float* returns_out, void* stream) {
+    if (num_steps < 1 || num_envs < 1) return fail("lb_gae_tl: num_steps < 1 or num_envs < 1");
+    if (!rewards || !values || !dones || !next_value || !next_done || !term_values || !advantages_out || !returns_out)
+        return fail("lb_gae_tl: a buffer is NULL");
+    const void* in[6] = {rewards, values, dones, next_value, next_done, term_values};
+    for (const void* q : in)
+        if (q == advantages_out || q == returns_out) return fail("lb_gae_tl: an output is also an input");
+    if (advantages_out == returns_out) return fail("lb_gae_tl: advantages_out == returns_out");
+    GAEParams p{rewards, values, dones, next_value, next_done, num_steps, num_envs,
+                (float)gamma, (float)(gamma * gae_lambda), advantages_out, returns_out};
+    const int64_t blocks = (num_envs + GAE_BLOCK - 1) / GAE_BLOCK;
+    if (blocks > 0x7FFFFFFF) return fail("lb_gae_tl: num_envs too large for one launch");
+    hipLaunchKernelGGL(k_gae_tl, dim3((unsigned)blocks), dim3(GAE_BLOCK), 0, (hipStream_t)stream, p, term_values);
     return check_launch();
 }
 

@@ -15,7 +15,20 @@
 // arithmetic is per set column, so the bits do not depend on P (lb_ds_sample itself takes P = 1,
 // 2 or 4 by the batch).  LDS: the image (135,440 B) plus 8 waves x 2 buffers x P x 34
 // float4s = 152,848 B at P = 2 (P = 4 would pass 160 KB).
+//
+// TL (k_ppo_steps<P, true>: lb_ppo_steps_tl, include/lbk8s_abi_ppo_tl.h): lb_step writes the finished
+// envs' terminal observations (e.term_obs, slice_apply) and each step leaves its term_values row:
+// +0 for an env that goes on and, where an env of the group finished (a wave-uniform test: 1 step
+// in episode_length), lb_ds_value_where's critic on the group's terminal observations, read back
+// from e.term_obs once the wave's stores are complete (no third LDS buffer fits, and none is
+// needed).  The step's own critic moves behind the env step there (its input is the six fragment
+// words of ds_group_obs, nothing of the env), so both critics are ONE site of the code, run once or
+// twice: two inlined copies spilled.  The flagged critic (DS_FWD_WHERE) with every flag set is the
+// sampling forward's critic, and its arithmetic is per set column: lb_ds_sample's and
+// lb_ds_value_where's bits.
 #pragma once
+
+#include <type_traits>
 
 #include "lbk8s_deepsets.h"
 #include "lbk8s_steps.h"
@@ -37,11 +50,16 @@ struct PPOSteps {
     StepsRecord rec;          // lb_ppo_record's sums and episode log
 };
 
+struct PPOStepsTL : PPOSteps {
+    float* term_values;       // [steps][B]
+};
+
 // d: the forward (lb_ds_sample's DSParams without masks or logits: actions = the caller's int32
-// action buffer); e: the env (lb_step's Params: done, ep_stats, no terminal obs; obs / reward
-// are the per-step rows of r).
-template <int P>
-__global__ __launch_bounds__(DS_BLOCK, 2) void k_ppo_steps(DSParams d, Params e, PPOSteps r) {
+// action buffer); e: the env (lb_step's Params: done, ep_stats, no terminal obs -- TL: the call's
+// terminal_obs; obs / reward are the per-step rows of r).
+template <int P, bool TL = false>
+__global__ __launch_bounds__(DS_BLOCK, 2) void k_ppo_steps(DSParams d, Params e,
+                                                           std::conditional_t<TL, PPOStepsTL, PPOSteps> r) {
     static_assert(P == 1 || P == 2, "envs per wave iteration (the LDS budget)");
     constexpr int NWB = DS_BLOCK / 64;
     __shared__ __attribute__((aligned(16))) float W[DS_FLOATS];
@@ -77,7 +95,7 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_ppo_steps(DSParams d, Params e,
             float h0[P][2], m0[2], xr0[2];
             ds_group_obs<1, P, LB_DS_FWD_SAMPLE>(ds, env0, col, grp, R, h0, m0, xr0, reinterpret_cast<const float*>(cur));
             const int32_t a = ds_group_actor<1, P, LB_DS_FWD_SAMPLE, false>(ds, W, lane, env0, col, grp, R, h0, m0);
-            ds_group_critic<1, P, LB_DS_FWD_SAMPLE, false>(ds, W, lane, env0, col, grp, R, h0, m0);
+            if constexpr (!TL) ds_group_critic<1, P, LB_DS_FWD_SAMPLE, false>(ds, W, lane, env0, col, grp, R, h0, m0);
             g.step(e, a, nxt);
             // the next observations' storage row, from LDS (the wave's LDS writes and reads complete
             // in order)
@@ -93,6 +111,25 @@ __global__ __launch_bounds__(DS_BLOCK, 2) void k_ppo_steps(DSParams d, Params e,
                 }
             }
             g.record(e, r.rec, a, i);
+            if constexpr (TL) {
+                // the step's critic, then lb_ds_value_where(frag, terminal_obs, done_out, ..) on the
+                // group where an env of it finished (fin: the finished envs' head lanes, 16 s)
+                const uint64_t fin = __ballot(g.head && g.dn);
+                if (g.head && !g.dn) r.term_values[row + env] = 0.f;
+                uint32_t fl = ~0u;
+#pragma clang loop unroll(disable)
+                for (int pass = 0;; ++pass) {
+                    ds_group_critic<1, P, DS_FWD_WHERE, false>(ds, W, lane, env0, col, grp, R, h0, m0, nullptr, nullptr, fl);
+                    if (pass || !fin) break;
+                    fl = 0;
+#pragma unroll
+                    for (int s = 0; s < P; ++s) fl |= (uint32_t)((fin >> (16 * s)) & 1) << s;
+                    __threadfence();  // the slices' terminal rows, stored by other lanes of the wave
+                    ds.obs = e.term_obs;
+                    ds.value = r.term_values + row;
+                    ds_group_obs<1, P, DS_FWD_WHERE>(ds, env0, col, grp, R, h0, m0, xr0, nullptr, fl);
+                }
+            }
         }
         g.close(e, &r.rec);
     }

@@ -60,6 +60,15 @@ int ppo_steps_launch(const PPOStepsCall& c) {
     return steps_launch(k_ppo_steps<STEPS_P>, c.num_envs, c.stream, d, e, r);
 }
 
+int ppo_steps_tl_launch(const PPOStepsCall& c) {
+    DSParams d;
+    Params e;
+    PPOStepsTL r;
+    ppo_steps_params(c, d, e, r);  // (e.term_obs: the call's terminal_obs)
+    r.term_values = c.term_values;
+    return steps_launch(k_ppo_steps<STEPS_P, true>, c.num_envs, c.stream, d, e, r);
+}
+
 int eval_steps_launch(const EvalStepsCall& c) {
     DSParams d;
     Params e;
@@ -141,6 +150,27 @@ int lb_ppo_steps(const float* frag, const float* obs, void* state, const lb_conf
     if (int rc = ppo_steps_check("lb_ppo_steps", c)) return rc;
     if (!steps_fusable(cfg, num_envs, num_elements)) return steps_unsupported("lb_ppo_steps", "rollout");
     return ppo_steps_launch(c);
+}
+
+// lb_ppo_steps with the terminal values (include/lbk8s_abi_ppo_tl.h): lb_ppo_steps' shape
+int lb_ppo_steps_tl_supported(const lb_config* cfg, int64_t num_envs, int32_t num_elements) {
+    return lb_ppo_steps_supported(cfg, num_envs, num_elements);
+}
+
+int lb_ppo_steps_tl(const float* frag, const float* obs, void* state, const lb_config* cfg, int64_t num_envs,
+                    int32_t num_elements, int32_t steps, int32_t store_rows, const float* uniforms, float* actions_f32,
+                    float* logprobs, float* values, float* rewards, float* obs_next, float* dones_next,
+                    float* last_obs, float* last_done, int32_t* actions_out, uint8_t* done_out, double* ep_stats_out,
+                    double* ep_sum, double* ep_cnt, float* ret32, float* ep_r32, int64_t tag0, double* log,
+                    int64_t cap, uint32_t* count, float* terminal_obs, float* term_values, void* stream) {
+    if (int r = validate(cfg)) return r;
+    const PPOStepsCall c{frag, obs, state, cfg, num_envs, num_elements, steps, store_rows, uniforms, actions_f32, logprobs,
+                         values, rewards, obs_next, dones_next, last_obs, last_done, actions_out, done_out, ep_stats_out,
+                         {ep_sum, ep_cnt, ret32, ep_r32, tag0, log, cap, count}, stream, terminal_obs, term_values};
+    if (int rc = ppo_steps_check("lb_ppo_steps_tl", c)) return rc;
+    if (!terminal_obs || !term_values) return steps_fail("lb_ppo_steps_tl", ": terminal_obs / term_values NULL");
+    if (!steps_fusable(cfg, num_envs, num_elements)) return steps_unsupported("lb_ppo_steps_tl", "rollout");
+    return ppo_steps_tl_launch(c);
 }
 
 // lb_eval_steps' shape is lb_ppo_steps' (the greedy forward in place of the sampling one)

@@ -33,6 +33,7 @@ struct PPOStepsCall {  // lb_ppo_steps' arguments (include/lbk8s.h)
     double* ep_stats_out;
     StepsRecord rec;
     void* stream;
+    float *terminal_obs = nullptr, *term_values = nullptr;  // lb_ppo_steps_tl's (else NULL)
 };
 
 struct EvalStepsCall {  // lb_eval_steps' arguments
@@ -85,6 +86,7 @@ struct DQNStepsCall {  // lb_dqn_steps' arguments (lb_dqn_step: steps = 1, no sy
 // k_eval_steps64's and k_dqn_steps64's, which are lb_ppo_steps256's, lb_eval_steps256's and
 // lb_dqn_steps256's at E <= 64 (lbk8s_steps64.hip; they hand the 16-lane shape on themselves)
 int ppo_steps_launch(const PPOStepsCall& c);
+int ppo_steps_tl_launch(const PPOStepsCall& c);
 int eval_steps_launch(const EvalStepsCall& c);
 int dqn_steps_launch(const DQNStepsCall& c);
 int ppo_steps64_launch(const PPOStepsCall& c);
@@ -126,6 +128,7 @@ inline int ppo_steps_check(const char* fn, const PPOStepsCall& c) {
 inline void ppo_steps_params(const PPOStepsCall& c, DSParams& d, Params& e, PPOSteps& r) {
     e = make_params(c.state, c.cfg, c.num_envs);
     e.done = c.done_out;
+    e.term_obs = c.terminal_obs;
     e.ep_stats = c.ep_stats_out;
     d = DSParams{nullptr, c.frag, nullptr, nullptr, c.num_envs, c.num_elements, 1, 1, nullptr, nullptr, nullptr, nullptr,
                  c.actions_out, nullptr};

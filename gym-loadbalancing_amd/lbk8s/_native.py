@@ -17,7 +17,8 @@ SOURCES = ("lbk8s_env_steps.hip", "lbk8s_env.hip", "lbk8s_ds.hip", "lbk8s_ds_tra
            "lbk8s_learn.hip", "lbk8s_host.h", "lbk8s_common.h", "lbk8s_slice.h", "lbk8s_tpe.h", "lbk8s_rollout.h", "lbk8s_lean.h",
            "lbk8s_deepsets.h", "lbk8s_ds_chunked.h", "lbk8s_ds_train.h", "lbk8s_steps.h", "lbk8s_dqn.h", "lbk8s_ppo.h", "lbk8s_eval.h",
            "../../include/lbk8s.h", "../../include/lbk8s_abi_steps64.h", "../../include/lbk8s_abi_dqn64.h",
-           "../../include/lbk8s_abi_steps256.h", "../../include/lbk8s_abi_dqn256.h", "../../include/lbk8s_abi_ppo256.h", "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_policies.hip", "lbk8s_steps64.h", "lbk8s_dqn64.h",
+           "../../include/lbk8s_abi_steps256.h", "../../include/lbk8s_abi_dqn256.h", "../../include/lbk8s_abi_ppo256.h", "../../include/lbk8s_abi_ppo_tl.h",
+           "lbk8s_lean_launch.h", "lbk8s_lean_inst.hip", "lbk8s_policies.hip", "lbk8s_steps64.h", "lbk8s_dqn64.h",
            "lbk8s_steps64.hip", "lbk8s_steps256.h", "lbk8s_dqn256.h", "lbk8s_ppo256.h", "lbk8s_steps256.hip", "lbk8s_steps_host.h",
            "lbk8s_build.cpp")
 ABI_VERSION = 17
@@ -188,6 +189,23 @@ PPO256_PROTOTYPES = {name.replace("_steps", "_steps256"): PROTOTYPES[name]
                      for name in ("lb_ppo_steps_supported", "lb_ppo_steps")}
 PPO256_SYMBOLS = tuple(PPO256_PROTOTYPES)
 
+
+def _ppo_tl_prototypes():
+    """include/lbk8s_abi_ppo_tl.h's prototypes (lbk8s_abi_ppo256.h includes it): PPO's value targets
+    that bootstrap from the terminal state at a time limit (tests/test_ppo_tl_host.py compares this
+    table with that header).  lb_gae_tl: lb_gae with term_values after next_done; lb_ppo_steps_tl:
+    lb_ppo_steps with terminal_obs and term_values before the stream."""
+    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
+    gae, steps = PROTOTYPES["lb_gae"][1], PROTOTYPES["lb_ppo_steps"][1]
+    return {"lb_gae_tl": (C.c_int, gae[:5] + [vp] + gae[5:]),
+            "lb_ds_value_where": (C.c_int, [vp, vp, vp, i64, i32, vp, vp]),
+            "lb_ppo_steps_tl_supported": PROTOTYPES["lb_ppo_steps_supported"],
+            "lb_ppo_steps_tl": (C.c_int, steps[:-1] + [vp, vp] + steps[-1:])}
+
+
+PPO_TL_PROTOTYPES = _ppo_tl_prototypes()
+PPO_TL_SYMBOLS = tuple(PPO_TL_PROTOTYPES)
+
 _lib = None
 
 
@@ -289,7 +307,7 @@ def lib():
         f = getattr(L, name)  # (a diagnostic library's stand-in where it lacks the symbol)
         f.restype, f.argtypes = restype, argtypes
     for name, (restype, argtypes) in {**STEPS64_PROTOTYPES, **DQN64_PROTOTYPES, **STEPS256_PROTOTYPES,
-                                       **DQN256_PROTOTYPES, **PPO256_PROTOTYPES}.items():
+                                       **DQN256_PROTOTYPES, **PPO256_PROTOTYPES, **PPO_TL_PROTOTYPES}.items():
         # (a product library is built from the tree's sources, checked below, and has them; in any
         # other, calling one raises: there is no stand-in and no fallback)
         if hasattr(L, name):

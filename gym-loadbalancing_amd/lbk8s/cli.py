@@ -95,6 +95,10 @@ def build_parser():
     p.add_argument("--fused-rollout-e256", action="store_true",
                    help="ppo_deepsets: a rollout's vector steps as one launch through lb_ppo_steps256 "
                         "(PPO_DeepSets(fused_rollout_e256=True)): E <= 256, R <= 257, fewer than 32,768 envs")
+    p.add_argument("--bootstrap-timeouts", action="store_true",
+                   help="ppo_deepsets: at an episode's end (always the time limit) bootstrap the value target "
+                        "from the critic's value of the terminal observation "
+                        "(PPO_DeepSets(bootstrap_timeouts=True)); an error for dqn_deepsets")
     p.add_argument("--dqn-steps-e64", action="store_true",
                    help="dqn_deepsets: a train period's vector steps as one launch through lb_dqn_steps64 "
                         "(DQN_DeepSets(multi_step_e64=True)): E <= 64, R <= 65, fewer than 32,768 envs")
@@ -158,7 +162,8 @@ def get_model(alg, env, rank=0, dqn_steps_e64=False, dqn_steps_e256=False, **ppo
     learner seed is offset by its rank, so rollout uniforms, minibatch permutations, replay
     samples and exploration coins differ across GPUs (the parameters are broadcast from rank
     0, so the replicas still start identical).  ppo_flags: PPO_DeepSets' fused_act /
-    fused_bookkeeping / fused_rollout / fused_rollout_e64 / fused_rollout_e256 (all off by default); dqn_steps_e64 /
+    fused_bookkeeping / fused_rollout / fused_rollout_e64 / fused_rollout_e256 / bootstrap_timeouts (all off by
+    default); dqn_steps_e64 /
     dqn_steps_e256: DQN_DeepSets' multi_step_e64 / multi_step_e256 (off by default)."""
     if alg == "ppo_deepsets":
         from .ppo import PPO_DeepSets
@@ -182,6 +187,10 @@ def model_name(alg, env_name, num_endpoints, num_zones, reward, total_steps):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = build_parser().parse_args(argv)
+    if args.bootstrap_timeouts and args.alg != "ppo_deepsets":  # (before any rank is spawned)
+        raise SystemExit(f"--bootstrap-timeouts is a ppo_deepsets option: {args.alg!r} has no value target that "
+                         "bootstraps from the terminal observation (DQN's replay stores the post-reset observation "
+                         "at a done)")
     if args.nproc > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # spawn the ranks before anything touches the GPU, then wait for them
         from .dist import launch
@@ -205,6 +214,8 @@ def main(argv=None):
                      fused_rollout=args.fused_rollout,
                      fused_rollout_e64=args.fused_rollout_e64,
                      fused_rollout_e256=args.fused_rollout_e256) if alg == "ppo_deepsets" else {}
+        if alg == "ppo_deepsets" and args.bootstrap_timeouts:
+            flags["bootstrap_timeouts"] = True
         if alg == "dqn_deepsets" and args.dqn_steps_e64:
             flags["dqn_steps_e64"] = True
         if alg == "dqn_deepsets" and args.dqn_steps_e256:

@@ -195,6 +195,35 @@ def deepsets_sample(agent, x: torch.Tensor, uniforms: torch.Tensor, masks=None, 
 
 
 @torch.no_grad()
+def deepsets_value_where(agent, x: torch.Tensor, flags: torch.Tensor, out: torch.Tensor):
+    """The critic's value of the flagged sets in one launch (lb_ds_value_where): out[b] is, bit for
+    bit, deepsets_forward's value of set b where flags[b] != 0, and +0.0 elsewhere, where x[b] is
+    not read (NaN or stale rows there have no effect: LBVecEnv.terminal_obs of the envs that did
+    not finish).  A launch with no flagged set does no forward work.
+
+    x (B, R, 8) float32 contiguous; flags (B,) uint8 or bool; out (B,) float32 (a storage row can be
+    passed as it is).  No allocation and no host synchronisation: capturable, as deepsets_sample.
+    Returns out."""
+    if not sample_supported(agent, x):
+        raise RuntimeError(f"fused deep-sets forward does not cover input {tuple(x.shape)} on {x.device}")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("deepsets_value_where: x must be a contiguous float32 tensor")
+    B, R, _ = x.shape
+    dev = x.device
+    if (not isinstance(flags, torch.Tensor) or flags.dtype not in (torch.uint8, torch.bool) or tuple(flags.shape) != (B,)
+            or not flags.is_contiguous() or flags.device != dev):
+        raise ValueError(f"deepsets_value_where: flags must be a contiguous ({B},) uint8 or bool tensor on {dev}")
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B,)
+            or not out.is_contiguous() or out.device != dev):
+        raise ValueError(f"deepsets_value_where: out must be a contiguous ({B},) float32 tensor on {dev}")
+    frag = packed(agent, agent.actor.net, agent.critic)
+    _native.check(_native.lib().lb_ds_value_where(
+        frag.data_ptr(), x.data_ptr(), flags.data_ptr(), B, R, out.data_ptr(),
+        torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+@torch.no_grad()
 def q_forward(qnet, x: torch.Tensor, require: bool = False):
     """Q values (B, R) of a DQNDeepSetAgent (actor-only image of its q_network)."""
     net = qnet.q_network.net

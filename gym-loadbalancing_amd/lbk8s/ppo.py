@@ -29,6 +29,13 @@ it (E <= 16 below 32,768 envs, R <= 16), and with fused_rollout_e64 where lb_ppo
 (E <= 64 below 32,768 envs, R <= 65, Philox mode: config 4), and with fused_rollout_e256 where
 lb_ppo_steps256 has it (E <= 256, R <= 257: the evaluation sweep's sizes).  All five flags are off by
 default.
+
+bootstrap_timeouts (off by default: the reference's behaviour) is partial-episode bootstrapping.
+Every episode of this env ends at its time limit, a truncation, and the observation holds no step
+index, so the reference's GAE trains the critic toward "return until a deadline it cannot see".
+With the option, at a `done` the TD error bootstraps from the critic's value of the episode's
+terminal observation (storage `term_values`, compute_gae_tl / gae_tl_device) and the lambda-chain
+is still cut there.
 """
 import os
 import time
@@ -104,10 +111,35 @@ def compute_gae(rewards, values, dones, next_value, next_done, gamma, gae_lambda
     return advantages, advantages + values
 
 
-def _gae_arg(name, t, shape, device):
+def compute_gae_tl(rewards, values, dones, next_value, next_done, term_values, gamma, gae_lambda):
+    """compute_gae with the bootstrap at a time limit, on (T, B) device tensors: where step t ended
+    the episode (dones[t + 1], or next_done at t = T - 1) the TD error takes term_values[t], the
+    critic's value of the episode's terminal observation, in place of values[t + 1] (the next
+    episode's first value); the lambda-chain is cut there as in compute_gae.  lb_gae_tl's
+    expression order (include/lbk8s_abi_ppo_tl.h): compute_gae's bits with term_values zero, and
+    with no done anywhere."""
+    T = rewards.shape[0]
+    advantages = torch.zeros_like(rewards)
+    lastgaelam = torch.zeros_like(rewards[0])
+    for t in reversed(range(T)):
+        if t == T - 1:
+            nextdone = next_done.reshape(-1)
+            nextvalues = next_value.reshape(-1)
+        else:
+            nextdone = dones[t + 1]
+            nextvalues = values[t + 1]
+        nextnonterminal = 1.0 - nextdone
+        bootstrap = torch.where(nextdone != 0, term_values[t], nextvalues)
+        delta = rewards[t] + gamma * bootstrap - values[t]
+        lastgaelam = delta + gamma * gae_lambda * nextnonterminal * lastgaelam
+        advantages[t] = lastgaelam
+    return advantages, advantages + values
+
+
+def _gae_arg(name, t, shape, device, who="gae_device"):
     if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape
             or not t.is_contiguous() or t.device != device):
-        raise ValueError(f"gae_device: {name} must be a contiguous {shape} torch.float32 tensor on {device}")
+        raise ValueError(f"{who}: {name} must be a contiguous {shape} torch.float32 tensor on {device}")
     return t
 
 
@@ -145,6 +177,36 @@ def gae_device(rewards, values, dones, next_value, next_done, gamma, gae_lambda,
     return adv, ret
 
 
+@torch.no_grad()
+def gae_tl_device(rewards, values, dones, next_value, next_done, term_values, gamma, gae_lambda, out=None):
+    """compute_gae_tl in one launch (lb_gae_tl): gae_device's arguments, checks and conventions,
+    plus term_values (T, B), a contiguous float32 tensor on the same device and distinct from the
+    outputs."""
+    who = "gae_tl_device"
+    if not isinstance(rewards, torch.Tensor) or rewards.dim() != 2:
+        raise ValueError(f"{who}: rewards must be a (T, B) tensor")
+    if rewards.device.type != "cuda":
+        raise ValueError(f"{who}: the tensors must be on a HIP device, not {rewards.device}")
+    T, B = rewards.shape
+    dev = rewards.device
+    for name, t in (("rewards", rewards), ("values", values), ("dones", dones), ("term_values", term_values)):
+        _gae_arg(name, t, (T, B), dev, who)
+    for name, t in (("next_value", next_value), ("next_done", next_done)):
+        if isinstance(t, torch.Tensor) and tuple(t.shape) == (1, B):
+            t = t.view(B)
+        _gae_arg(name, t, (B,), dev, who)
+    if out is None:
+        out = (torch.empty_like(rewards), torch.empty_like(rewards))
+    adv, ret = out
+    _gae_arg("out[0]", adv, (T, B), dev, who)
+    _gae_arg("out[1]", ret, (T, B), dev, who)
+    _native.check(_native.lib().lb_gae_tl(
+        rewards.data_ptr(), values.data_ptr(), dones.data_ptr(), next_value.data_ptr(), next_done.data_ptr(),
+        term_values.data_ptr(), T, B, float(gamma), float(gae_lambda), adv.data_ptr(), ret.data_ptr(),
+        torch.cuda.current_stream(dev).cuda_stream))
+    return adv, ret
+
+
 class PPO_DeepSets:
     def __init__(self, env, learning_rate: float = 2.5e-4, anneal_lr: bool = False, num_steps: int = 128,
                  gae: bool = True, gae_lambda: float = 0.97, gamma: float = 0.95, n_minibatches: int = 4,
@@ -153,7 +215,8 @@ class PPO_DeepSets:
                  max_grad_norm: float = 0.5, target_kl: Optional[float] = None, seed: int = 1,
                  device=None, log_fn=None, num_envs=None, tensorboard_log=None, use_graphs=None,
                  fused_act: bool = False, fused_bookkeeping: bool = False, fused_rollout: bool = False,
-                 fused_rollout_e64: bool = False, fused_rollout_e256: bool = False):
+                 fused_rollout_e64: bool = False, fused_rollout_e256: bool = False,
+                 bootstrap_timeouts: bool = False):
         # fused_act: the rollout's policy step as ONE launch (fused.deepsets_sample) that writes the
         # env's action buffer and the step's storage rows (actions, logprobs, values) directly.  Off
         # by default: a draw on a CDF boundary can pick the neighbouring row (and u = 0 never picks
@@ -175,6 +238,14 @@ class PPO_DeepSets:
         # fused_rollout_e256: the same through LBVecEnv.ppo_steps256, whose shapes reach 256 endpoints
         # (ppo_steps256_supported: R <= 257; a superset: it serves E <= 64 too and takes precedence
         # where both are on).  Off by default.
+        # bootstrap_timeouts: at a `done` (always a time limit here) the value target bootstraps from
+        # the critic's value of the terminal observation (storage term_values (T, B), filled during
+        # the rollout; compute_gae_tl / gae_tl_device in update()).  The one-launch rollout is then
+        # LBVecEnv.ppo_steps_tl, which has lb_ppo_steps' shapes: with any fused_rollout* flag on and
+        # ppo_steps_supported, fused_rollout reads True and the other two False; on every other
+        # shape the per-step path runs (one more launch per step, fused.deepsets_value_where, or its
+        # torch equivalent where the fused forward does not cover the agent).  Off by default: the
+        # reference treats every done as a true terminal.
         # num_envs / tensorboard_log: accepted for signature compatibility with
         # ppo_deepset.py:53-75 (the env's num_envs is used; there is no tensorboard writer)
         self.env = env
@@ -240,6 +311,15 @@ class PPO_DeepSets:
         self.fused_rollout_e256 = (bool(fused_rollout_e256) and dev.type == "cuda" and hasattr(env, "ppo_steps256")
                                    and fused.sample_supported(self.agent, self.obs[0])
                                    and env.ppo_steps256_supported(R))
+        self.bootstrap_timeouts = bool(bootstrap_timeouts)
+        if self.bootstrap_timeouts:  # the one-launch rollout with terminal values has lb_ppo_steps' shapes only
+            self.fused_rollout = ((bool(fused_rollout) or bool(fused_rollout_e64) or bool(fused_rollout_e256))
+                                  and dev.type == "cuda" and hasattr(env, "ppo_steps_tl")
+                                  and fused.sample_supported(self.agent, self.obs[0]) and env.ppo_steps_supported(R))
+            self.fused_rollout_e64 = self.fused_rollout_e256 = False
+            self.term_values = torch.zeros((T, B), device=dev)
+            # the per-step path's route, decided once: one launch where the fused forward covers the agent
+            self._tv_fused = hasattr(env, "terminal_obs") and fused.sample_supported(self.agent, env.terminal_obs)
         self.fused_rollout = self.fused_rollout or self.fused_rollout_e64 or self.fused_rollout_e256
         if self.fused_rollout:  # (its buffers are fused_bookkeeping's; GAE in one launch too)
             self.fused_bookkeeping = True
@@ -260,9 +340,12 @@ class PPO_DeepSets:
             agent = self.agent
             steps = (env.ppo_steps256 if self.fused_rollout_e256
                      else env.ppo_steps64 if self.fused_rollout_e64 else env.ppo_steps)
+            tl = {}
+            if self.bootstrap_timeouts:
+                steps, tl = env.ppo_steps_tl, dict(term_values=self.term_values)
             steps(fused.packed(agent, agent.actor.net, agent.critic), self.obs[0], self._u, self.actions,
                   self.logprobs, self.values, self.rewards, self.obs[1:], self.dones[1:], self._last_obs,
-                  self._next_done, self._act, self._done_u8, self._ep_sum, self._ep_cnt)
+                  self._next_done, self._act, self._done_u8, self._ep_sum, self._ep_cnt, **tl)
             return self._next_done
         next_obs = self.obs[0]
         fb = self.fused_bookkeeping
@@ -284,6 +367,8 @@ class PPO_DeepSets:
             # the env writes the next observation straight into the next storage slot
             next_obs = self.obs[step + 1] if step + 1 < T else self._last_obs
             env.step_device(self._act, obs_out=next_obs, reward_out=self.rewards[step], done_out=self._done_u8)
+            if self.bootstrap_timeouts:  # V(terminal observation) of the envs that finished, 0 elsewhere
+                self._terminal_values(self.term_values[step])
             if fb:  # one launch: the next done row, the episode sums, the VecMonitor log
                 next_done = self.dones[step + 1] if step + 1 < T else self._next_done
                 env.record_ppo(self._done_u8, self.rewards[step], self._act, next_done, self._ep_sum, self._ep_cnt)
@@ -294,6 +379,20 @@ class PPO_DeepSets:
             self._ep_sum += (env.ep_stats[:, 0] * next_done).sum()
             self._ep_cnt += next_done.sum()
         return next_done
+
+    def _terminal_values(self, out):
+        """out (B,) = the critic's value of env.terminal_obs where the last step_device finished the
+        env (self._done_u8), else 0: one launch where the fused forward covers the agent."""
+        env = self.env
+        if self._tv_fused:
+            fused.deepsets_value_where(self.agent, env.terminal_obs, self._done_u8, out=out)
+            return
+        done = self._done_u8 != 0
+        # (an unfinished env's terminal_obs row is stale or unwritten: it must not reach the output)
+        x = torch.where(done.view(-1, 1, 1), env.terminal_obs, torch.zeros_like(env.terminal_obs))
+        with torch.no_grad():
+            v = self.agent.get_value(x).reshape(-1)
+        out.copy_(torch.where(done, v, torch.zeros_like(v)))
 
     def rollout(self, next_obs, next_done):
         """Fill the (T, B) storage; returns the obs/done that follow the last step."""
@@ -340,7 +439,13 @@ class PPO_DeepSets:
     def update(self, next_obs, next_done):
         with torch.no_grad():
             next_value = self.agent.get_value(next_obs).reshape(1, -1)
-            if self.fused_bookkeeping:  # one launch into the preallocated buffers
+            if self.bootstrap_timeouts and self.fused_bookkeeping:
+                advantages, returns = gae_tl_device(self.rewards, self.values, self.dones, next_value, next_done,
+                                                    self.term_values, self.gamma, self.gae_lambda, out=self._gae_out)
+            elif self.bootstrap_timeouts:
+                advantages, returns = compute_gae_tl(self.rewards, self.values, self.dones, next_value, next_done,
+                                                     self.term_values, self.gamma, self.gae_lambda)
+            elif self.fused_bookkeeping:  # one launch into the preallocated buffers
                 advantages, returns = gae_device(self.rewards, self.values, self.dones, next_value, next_done,
                                                  self.gamma, self.gae_lambda, out=self._gae_out)
             else:

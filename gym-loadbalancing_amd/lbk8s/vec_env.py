@@ -505,9 +505,30 @@ class LBVecEnv:
         return self._ppo_steps("ppo_steps", self._L.lb_ppo_steps, frag, obs, uniforms, actions_f32, logprobs, values,
                                rewards, obs_next, dones_next, last_obs, last_done, actions, dones, ep_sum, ep_cnt)
 
+    def ppo_steps_tl_supported(self, R):
+        """Whether lb_ppo_steps_tl (ppo_steps with the terminal values) covers this env with R-row
+        observations: ppo_steps_supported's answer."""
+        return bool(self._L.lb_ppo_steps_tl_supported(C.byref(self._c), self.num_envs, R))
+
+    def ppo_steps_tl(self, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next, dones_next,
+                     last_obs, last_done, actions, dones, ep_sum, ep_cnt, term_values):
+        """lb_ppo_steps_tl: ppo_steps, argument for argument, and the rollout's terminal values.  Each
+        step's lb_step also writes the finished envs' pre-reset observations to self.terminal_obs,
+        and row i of term_values (T, B) float32 is fused.deepsets_value_where(frag's agent,
+        terminal_obs, step i's dones): the critic's value of the terminal observation of the envs
+        that finished in step i, +0.0 for the rest -- bit for bit that launch after every step.
+        self.terminal_obs ends as every env's last terminal observation (untouched for an env that
+        never finished).  The shapes of ppo_steps_supported; split at the monitor's flushes as
+        ppo_steps."""
+        return self._ppo_steps("ppo_steps_tl", self._L.lb_ppo_steps_tl, frag, obs, uniforms, actions_f32, logprobs,
+                               values, rewards, obs_next, dones_next, last_obs, last_done, actions, dones, ep_sum,
+                               ep_cnt, term_values=term_values)
+
     def _ppo_steps(self, who, entry, frag, obs, uniforms, actions_f32, logprobs, values, rewards, obs_next,
-                   dones_next, last_obs, last_done, actions, dones, ep_sum, ep_cnt):
-        """ppo_steps / ppo_steps64 / ppo_steps256 (who: the method's name, entry: its library function)."""
+                   dones_next, last_obs, last_done, actions, dones, ep_sum, ep_cnt, term_values=None):
+        """ppo_steps / ppo_steps64 / ppo_steps256 / ppo_steps_tl (who: the method's name, entry: its
+        library function; term_values: ppo_steps_tl's, whose entry takes terminal_obs and its rows
+        before the stream)."""
         t = self.torch
         if not self._reset_called and not t.cuda.is_current_stream_capturing():
             raise TypeError("step() called before reset()")
@@ -530,6 +551,10 @@ class LBVecEnv:
             ("dones", dones, (B,), t.uint8, False), ("ep_sum", ep_sum, (B,), t.float64, False),
             ("ep_cnt", ep_cnt, (B,), t.float64, False), ("last_obs", last_obs, (B, R, 8), t.float32, last),
             ("last_done", last_done, (B,), t.float32, last)])
+        tl = who == "ppo_steps_tl"
+        if tl:
+            self._check_tensors(who, [("term_values", term_values, (T, B), t.float32, False),
+                                      ("terminal_obs", self.terminal_obs, (B, R, 8), t.float32, False)])
         if not getattr(self, who + "_supported")(R):
             raise RuntimeError(f"{who}: the env's shape has no one-launch rollout ({who}_supported)")
         for i, n in self._launches(T, _native.LB_PPO_STEPS_MAX):
@@ -541,7 +566,8 @@ class LBVecEnv:
                 self._ptr(rewards[i]), self._ptr(obs_next[i]) if s else None,
                 self._ptr(dones_next[i]) if s else None, self._ptr(last_obs) if s < n else None,
                 self._ptr(last_done) if s < n else None, self._ptr(actions), self._ptr(dones),
-                self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt), *self._log_args(), self._stream()))
+                self._ptr(self.ep_stats), self._ptr(ep_sum), self._ptr(ep_cnt), *self._log_args(),
+                *((self._ptr(self.terminal_obs), self._ptr(term_values[i])) if tl else ()), self._stream()))
             self._logged(n)
 
     def eval_steps_supported(self, R):

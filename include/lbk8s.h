@@ -552,7 +552,9 @@ int lb_eval_steps(const float* frag, float* obs, void* state, const lb_config* c
  * same envs: lbk8s_abi_dqn64.h, included there too.  lb_eval_steps256 and its _supported query,
  * lb_eval_steps for envs of up to 256 endpoints (R <= 257): lbk8s_abi_steps256.h, likewise.  lb_dqn_steps256 and
  * its _supported query, lb_dqn_steps for those envs: lbk8s_abi_dqn256.h, after it.  lb_ppo_steps256 and
- * its _supported query, lb_ppo_steps for those envs: lbk8s_abi_ppo256.h, last. */
+ * its _supported query, lb_ppo_steps for those envs: lbk8s_abi_ppo256.h, last.  lb_gae_tl,
+ * lb_ds_value_where, lb_ppo_steps_tl and its _supported query, PPO's value targets that bootstrap
+ * from the terminal state at a time limit: lbk8s_abi_ppo_tl.h, which that last header includes. */
 
 /* ---- Fused deep-sets training -----------------------------
  * Replaces the reference's autograd through the same modules in the PPO update

@@ -35,4 +35,8 @@ int lb_ppo_steps256(const float* frag, const float* obs, void* state, const lb_c
                     float* ret32, float* ep_r32, int64_t tag0, double* log, int64_t cap, uint32_t* count,
                     void* stream);
 
+/* ---- ABI 17, additions: lb_gae_tl, lb_ds_value_where, lb_ppo_steps_tl and its _supported query
+ * (PPO value targets that bootstrap from the terminal state at a time limit) */
+#include "lbk8s_abi_ppo_tl.h"
+
 #endif /* LBK8S_ABI_PPO256_H */

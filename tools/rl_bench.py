@@ -71,6 +71,10 @@ def parse():
     ap.add_argument("--fused-rollout-e256", action="store_true",
                     help="PPO: the rollout's vector steps as one launch through lb_ppo_steps256 "
                          "(PPO_DeepSets(fused_rollout_e256=True)): E <= 256, R <= 257 (--endpoints)")
+    ap.add_argument("--bootstrap-timeouts", action="store_true",
+                    help="PPO: value targets bootstrap from the terminal observation at a time limit "
+                         "(PPO_DeepSets(bootstrap_timeouts=True)): lb_ppo_steps_tl with --fused-rollout on its "
+                         "shapes, else one more launch per step (lb_ds_value_where)")
     ap.add_argument("--dqn-steps-e64", action="store_true",
                     help="DQN: a train period's vector steps as one launch through lb_dqn_steps64 "
                          "(DQN_DeepSets(multi_step_e64=True)): E <= 64, R <= 65, so --config e64_multi too")
@@ -131,8 +135,9 @@ def main():
         ppo = PPO_DeepSets(env, num_steps=args.num_steps, n_minibatches=8, update_epochs=4, ent_coef=0.001,
                            gamma=0.95, gae_lambda=0.97, seed=1, device=dev, fused_act=args.fused_act,
                            fused_bookkeeping=args.fused_bookkeeping, fused_rollout=args.fused_rollout,
-                           fused_rollout_e64=args.fused_rollout_e64, fused_rollout_e256=args.fused_rollout_e256)
-        out.update(fused_act=ppo.fused_act, fused_bookkeeping=ppo.fused_bookkeeping, fused_rollout=ppo.fused_rollout,
+                           fused_rollout_e64=args.fused_rollout_e64, fused_rollout_e256=args.fused_rollout_e256,
+                           bootstrap_timeouts=args.bootstrap_timeouts)
+        out.update(bootstrap_timeouts=ppo.bootstrap_timeouts, fused_act=ppo.fused_act, fused_bookkeeping=ppo.fused_bookkeeping, fused_rollout=ppo.fused_rollout,
                    fused_rollout_e64=ppo.fused_rollout_e64, fused_rollout_e256=ppo.fused_rollout_e256)
         next_obs = env.reset()
         next_done = torch.zeros(B, device=dev)
